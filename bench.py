@@ -30,6 +30,14 @@ contract: slab / non-uniform flow 1024 x 1024 both modes; cylinder / non-uniform
 rotational flow m = 0..10 with fp32 screening + fp64 refinement.  Their units (modes / azimuthal orders) run on one HIP
 stream each; N > 1: every rank owns the k-rows r, r + N, ... of EVERY unit (equal point counts), one all-gather per step.
 
+A plain run sets up, warms up, times the --steps steps and prints the line.  --full also measures what the headline
+figure does not need: the CPU baselines (before the GPU is initialised), the time of the dominant kernel alone on the
+chip (`roofline.avg_launch_ms_unshared`, from the back-to-back launches that end every warm-up) and, for the headline
+workload, the other continuum mode after the timed region.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64 / float32): the root table, and
+for the headline a fixed seeded sample of D(k, omega) and of the point statuses.  The inputs depend on the arguments
+only, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -84,6 +92,43 @@ def workload_grid():
     k = np.linspace(0.01, 4.0, NK)
     W = W_LO + (np.arange(NW, dtype=np.float64) + 0.5) * ((W_HI - W_LO) / NW)
     return k, W
+
+
+DUMP_GRID_SAMPLE = 1 << 20                    # grid points of D / status written by --dump-outputs (20 MB with the index)
+DUMP_SEED = 20260305
+
+
+def grid_sample_index(n_points):
+    """Flat indices of the grid points --dump-outputs writes: a fixed seeded sample, sorted (all points if fewer)."""
+    if n_points <= DUMP_GRID_SAMPLE:
+        return np.arange(n_points, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_points, DUMP_GRID_SAMPLE, replace=False))
+
+
+def dump_outputs(out_dir, roots, grid=None):
+    """--dump-outputs: `roots` maps column name -> 1-D array of the root table; `grid` is (D, status) of the last step
+    (torch tensors of one shape), of which the points at grid_sample_index are written."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"roots_" + key: np.asarray(v, dtype=np.float64) for key, v in roots.items()}
+    if grid is not None:
+        D_, st = grid
+        idx = grid_sample_index(D_.numel())
+        idx_t = torch.as_tensor(idx, device=D_.device)
+        arrays["grid_sample_index"] = idx.astype(np.float64)
+        arrays["grid_D_sample"] = D_.reshape(-1)[idx_t].cpu().numpy().astype(np.float64)
+        arrays["grid_status_sample"] = st.reshape(-1)[idx_t].cpu().numpy().astype(np.float32)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+def root_columns(t, count, unit, rows):
+    """Host copy of the first `count` records of a root table dict `t`, its row index mapped through `rows` (global
+    k-row of each local row) and the unit (azimuthal order / mode id) added as a column."""
+    cols = {key: t[key][:count].cpu().numpy() for key in ("k", "w", "w_lo", "w_hi", "resid", "flag")}
+    cols["unit"] = np.full(count, float(unit))
+    cols["row"] = rows[t["row"][:count].long()].cpu().numpy()
+    return cols
 
 
 def _pmc_file(workload):
@@ -277,6 +322,13 @@ def main():
                          "evaluates every point; the skip mode is then measured after the timed region and reported "
                          "under config.skip_continuum_mode")
     ap.add_argument("--dump-roots", default=None, help="write the merged root table of the last step to this .npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy: the root table "
+                         "(roots_<column>.npy) and, for the headline, a fixed seeded sample of D and of the point statuses "
+                         "(grid_D_sample.npy, grid_status_sample.npy at the flat indices grid_sample_index.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baselines, the time of the dominant "
+                         "kernel alone on the chip, and (headline workload) the other continuum mode after the timed region")
     ap.add_argument("--streams", type=int, default=3,
                     help="software pipelining of consecutive steps: S library contexts (HIP streams), each driven by its own "
                          "host thread; the latency-bound refinement of step i overlaps the grid launches of steps i + 1, i + 2")
@@ -309,7 +361,7 @@ def main():
     eq = workload_equilibrium()
     k_np, W_np = workload_grid()
     cpu = None
-    if not a.no_cpu_baseline and world == 1:          # timed on rank 0 at N = 1 only, before the GPU is initialised
+    if a.full and not a.no_cpu_baseline and world == 1:   # timed on rank 0 at N = 1 only, before the GPU is initialised
         cpu = cpu_baselines(eq, 1, k_np, W_np)
 
     import torch
@@ -370,11 +422,12 @@ def main():
     grid_lock = threading.Lock()
     grid_tail = [None]                             # event after the most recent grid launch of any lane
     no_gate = os.environ.get("ES_BENCH_NO_GATE") == "1"     # A/B aid: grid launches of the lanes not ordered
+    last_grid = [None]                             # --dump-outputs: (D, status) of the last timed step
 
-    def compute(j, ev=None):
+    def compute(j, ev=None, keep=False):
         """One pass of the hot path over the rank's tile on lane j, everything enqueued and NOTHING read back: grid, bracket
         flags + scan + emit, refinement with the count in device memory (es_shoot_find_roots_async), send buffer of the
-        exchange; `done` marks their completion on the lane's stream."""
+        exchange; `done` marks their completion on the lane's stream.  keep: hold on to this step's (D, status)."""
         stream, cx, pr, tb, cnt = lanes[j]
         with torch.cuda.stream(stream):
             # grid launches of different lanes run one after the other (each has the whole chip, and the events below
@@ -394,6 +447,8 @@ def main():
             send = D.pack_fixed(roots, cnt, m, rows_t, exchange_cap, ctx=cx) if exchange_cap else None
             done = torch.cuda.Event()
             done.record(stream)
+            if keep:
+                last_grid[0] = (D_, st)
         return roots, cnt, send, st, done
 
     def exchange(send, done):
@@ -403,8 +458,8 @@ def main():
         send.record_stream(cur)                        # allocated on the lane's stream, read by the collective on this one
         return D.gather_fixed(send, world)
 
-    def step(ev=None):
-        roots, cnt, send, st, done = compute(0, ev)
+    def step(ev=None, keep=False):
+        roots, cnt, send, st, done = compute(0, ev, keep)
         buf = exchange(send, done) if world > 1 else None
         return roots, cnt, buf, st
 
@@ -414,10 +469,10 @@ def main():
     for j in range(n_lanes):
         free_lanes.put(j)
 
-    def pipelined(ev):
+    def pipelined(ev, keep=False):
         j = free_lanes.get()
         try:
-            return compute(j, ev)
+            return compute(j, ev, keep)
         finally:
             free_lanes.put(j)
 
@@ -429,29 +484,33 @@ def main():
                 exchange(send_w, done_w)            # also brings the communicator up before the timed region
             torch.cuda.synchronize()
             assert int(cnt_w.item()) <= table_cap, (int(cnt_w.item()), table_cap)
-    # the dominant kernel alone on a busy chip: grid launches back to back on one stream, the first one not counted (a
-    # launch that follows idle time runs up to 13 % slower while the clocks ramp: tools/probe/time_small_launches.py)
+    # the end of the warm-up: grid launches back to back on one stream, so that the timed steps start on a busy chip (a
+    # launch that follows idle time runs up to 13 % slower while the clocks ramp: tools/probe/time_small_launches.py);
+    # --full times them: the dominant kernel alone on a busy chip, the first one not counted
     alone = []
     with torch.cuda.stream(lanes[0][0]):
         for _ in range(4):
-            e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            e[0].record(lanes[0][0])
+            e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if a.full else None
+            if e:
+                e[0].record(lanes[0][0])
             prob.eval_grid(k, W, skip_continuum=skip)
-            e[1].record(lanes[0][0])
-            alone.append(e)
+            if e:
+                e[1].record(lanes[0][0])
+                alone.append(e)
     torch.cuda.synchronize()
     unshared = [e0.elapsed_time(e1) for e0, e1 in alone[1:]]
     events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
     pool = ThreadPoolExecutor(max_workers=n_lanes) if n_lanes > 1 else None
+    keep_last = bool(a.dump_outputs)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if pool is None:
         for i in range(a.steps):
-            roots, cnt, buf, st = step(events[i])
+            roots, cnt, buf, st = step(events[i], keep_last and i == a.steps - 1)
     else:
-        futs = [pool.submit(pipelined, events[i]) for i in range(a.steps)]
+        futs = [pool.submit(pipelined, events[i], keep_last and i == a.steps - 1) for i in range(a.steps)]
         for f in futs:
             roots, cnt, send, st, done = f.result()
             buf = exchange(send, done) if world > 1 else None
@@ -463,10 +522,14 @@ def main():
     if nbr > table_cap:
         raise SystemExit(f"bracket count {nbr} exceeds the table capacity {table_cap} sized during warm-up")
     roots = {key: v[:nbr].clone() for key, v in roots.items()}     # the lane's table is reused by the steps below
+    if a.dump_outputs and world == 1:
+        dump_outputs(a.dump_outputs, root_columns(roots, nbr, m, rows_t), last_grid[0])
+    last_grid[0] = None
 
-    # the other mode of the grid evaluation, a few steps outside the timed region (N = 1 only): reported, never `value`
+    # --full: the other mode of the grid evaluation, a few steps outside the timed region (N = 1 only): reported, never
+    # `value`
     other = None
-    if world == 1 and share == 1 and not a.no_extra_mode:
+    if a.full and world == 1 and share == 1 and not a.no_extra_mode:
         st_main = st
         skip = not skip
         step()
@@ -514,6 +577,8 @@ def main():
     if rank == 0:
         if a.dump_roots and merged is not None:
             np.save(a.dump_roots, merged)
+        if a.dump_outputs and world > 1:                 # the merged table of all ranks
+            dump_outputs(a.dump_outputs, dict(zip(("k", "w", "unit", "resid", "flag", "row"), merged.T)))
         sections, rounds, ev_per_bracket = refine_plan(nbr)          # rank 0's tile (the ranks' counts may differ)
         evals_per_step = grid_points + refine_evals
         value = evals_per_step * a.steps / dt
@@ -651,7 +716,7 @@ def main_units(a):
     if a.gpus != world:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}")
     cpu = None
-    if not a.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only, before the GPU is initialised
+    if a.full and not a.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only, before the GPU is initialised
         u0 = units[len(units) // 2]
         cpu = cpu_baselines(u0[2], u0[4], u0[5], u0[6], mode=u0[3], numpy_leg=False)[0]
         cpu["sample"] = f"unit {u0[0]}: " + cpu["sample"]
@@ -811,19 +876,22 @@ def main_units(a):
     for unit_lanes in lanes:
         for ln in unit_lanes:
             ln["ctx"].grid_time()
-    # the dominant kernel alone on the chip: grid-march launches of the middle unit back to back (first not counted)
+    # the end of the warm-up: grid-march launches of the middle unit back to back, so that the timed steps start on a busy
+    # chip; --full times them: the dominant kernel alone on the chip (first not counted)
     mid = work[len(work) // 2]
     alone = []
     with torch.cuda.stream(mid["stream"]):
         for _ in range(4):
-            e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            e[0].record(mid["stream"])
+            e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if a.full else None
+            if e:
+                e[0].record(mid["stream"])
             if mixed:
                 mid["prob"].screen_grid(mid["k"], mid["W"])
             else:
                 mid["prob"].eval_grid(mid["k"], mid["W"])
-            e[1].record(mid["stream"])
-            alone.append(e)
+            if e:
+                e[1].record(mid["stream"])
+                alone.append(e)
     torch.cuda.synchronize()
     mid["ctx"].grid_time()
     unshared = [e0.elapsed_time(e1) for e0, e1 in alone[1:]]
@@ -849,6 +917,15 @@ def main_units(a):
         nbr += c
         nacc += int((item["table"][0]["flag"][:c] == 1).sum())
         nre += item["nre"]
+    if a.dump_outputs and world == 1:
+        parts = []
+        for unit_lanes in lanes:
+            ln = unit_lanes[(a.steps - 1) % n_lanes]       # the lane that ran the unit's last step
+            c = ln["count"] if mixed else int(ln["cnt"].item())
+            if c > ln["cap"]:
+                raise SystemExit(f"unit {ln['label']}: bracket count {c} exceeds the table capacity {ln['cap']}")
+            parts.append(root_columns(ln["table"][0], c, ln["uid"], ln["rows"]))
+        dump_outputs(a.dump_outputs, {key: np.concatenate([p[key] for p in parts]) for key in parts[0]})
     cdev = dev if backend == "nccl" else torch.device("cpu")
     tmax = torch.tensor([dt, grid_ms_local], dtype=torch.float64, device=cdev)
     grid_points_local = sum(item["nk"] * item["nw"] for item in work)
@@ -873,6 +950,8 @@ def main_units(a):
     if rank == 0:
         if a.dump_roots and merged is not None:
             np.save(a.dump_roots, merged)
+        if a.dump_outputs and world > 1:                 # the merged table of all ranks
+            dump_outputs(a.dump_outputs, dict(zip(("k", "w", "unit", "resid", "flag", "row"), merged.T)))
         _, rounds, ev_per_bracket = refine_plan()
         evals = grid_points + nre + nbr * ev_per_bracket
         value = evals * a.steps / dt

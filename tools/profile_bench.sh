@@ -19,6 +19,7 @@ rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAV
 # the PMC summary of THIS box first (profiles/pmc_latest_<workload>.json), then the bench line that quotes it: traffic,
 # valu_issue and the launch times of one line come from one box and one build
 cd $R && python $R/tools/summarize_profiles.py $TAG $WL > /dev/null || exit 5
+ARGS="$ARGS --full"      # the quoted line also carries the CPU baselines and the launch time alone on the chip
 python $R/bench.py $ARGS > $R/gpurun_out/bench_${TAG}${SUF}.json 2> $R/gpurun_out/bench_${TAG}${SUF}.err || { tail -5 $R/gpurun_out/bench_${TAG}${SUF}.err; exit 1; }
 tail -c 1500 $R/gpurun_out/bench_${TAG}${SUF}.json
 ls $R/gpurun_out | grep "${TAG}${SUF}" | head -20
