@@ -18,6 +18,8 @@
 //    the final classification with the reference's acceptance measure.  Both cylinder families launch one round / one step
 //    per launch (ONE); the bracket count may stay on the device (es_shoot_find_roots_async).
 //  * shoot_grid_f32_kernel: fp32 screening march of es_shoot_find_roots_mixed.
+//  * *_dcount_kernel: the re-evaluation / bracket-end steps of the mixed search with their counts in device memory
+//    (es_shoot_find_roots_screened_async): launches sized for the grid or the table capacity.
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
@@ -933,6 +935,72 @@ __global__ __launch_bounds__(256) void bracket_ends_store_kernel(const double* _
   if (!(pst[i] == ES_PT_OK && pst[n + i] == ES_PT_OK && a * b < 0.0)) atomicAdd(violations, 1);
 }
 
+// ---- the same steps with the counts in device memory (es_shoot_find_roots_screened_async) ------------------------------
+// The host knows only the grid size and the table capacity: every launch below is sized for those, reads its count from
+// the caller's count words (d_counts[0] brackets, [1] unsure points, [2] bracket-end points) and its workgroups beyond the
+// count return at once.  The arithmetic is that of the kernels above, line for line.
+
+// shoot_points_kernel with n = *d_n; one workgroup per 256 points of the launch bound.  The early exit is workgroup-
+// uniform and comes before shoot_point's LDS staging, whose barriers every lane of a live workgroup reaches.
+template <int FAM>
+__global__ __launch_bounds__(256) void shoot_points_dcount_kernel(ShootDev P, const double* __restrict__ kv,
+                                                                  const double* __restrict__ wv, const int* __restrict__ d_n,
+                                                                  double* __restrict__ Dout, uint8_t* __restrict__ stout) {
+  ES_POINT_LDS(FAM);
+  const int n = *d_n;
+  if ((long)blockIdx.x * 256 >= (long)n) return;                                          // workgroup-uniform
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = i < n;
+  const double k = in ? kv[i] : 1.0;
+  const double w = in ? wv[i] : 1.0;
+  double D, rel; uint8_t st;
+  shoot_point<FAM>(P, k, w, w, D, rel, st, es_point_lds);
+  if (in) {
+    Dout[i] = D;
+    stout[i] = st;
+  }
+}
+
+__global__ __launch_bounds__(256) void scatter_points_dcount_kernel(const long* __restrict__ pcell,
+                                                                    const double* __restrict__ pD,
+                                                                    const uint8_t* __restrict__ pst,
+                                                                    const int* __restrict__ d_n, double* __restrict__ D,
+                                                                    uint8_t* __restrict__ st) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)*d_n) return;
+  D[pcell[i]] = pD[i];
+  st[pcell[i]] = pst[i];
+}
+
+// bracket_ends_kernel for n = min(d_counts[0], capacity) brackets ([0, n) lower ends, [n, 2n) upper ends); the point
+// count 2n goes to d_counts[2] for the fp64 evaluation that follows
+__global__ __launch_bounds__(256) void bracket_end_points_dcount_kernel(es_root_table tab, int32_t* d_counts,
+                                                                  double* __restrict__ pk, double* __restrict__ pw) {
+  const int total = d_counts[0];
+  const int n = total < tab.capacity ? total : tab.capacity;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) d_counts[2] = 2 * n;
+  if (i >= n) return;
+  pk[i] = tab.d_k[i]; pk[n + i] = tab.d_k[i];
+  pw[i] = tab.d_w_lo[i]; pw[n + i] = tab.d_w_hi[i];
+}
+
+// the fp64 end values of the n = min(d_counts[0], cap) brackets go where the refinement reads them (the arithmetic of
+// the kernel above); violations are counted into d_counts[3]
+__global__ __launch_bounds__(256) void bracket_end_values_dcount_kernel(const double* __restrict__ pD,
+                                                                        const uint8_t* __restrict__ pst, int32_t* d_counts,
+                                                                        int cap, double* __restrict__ d_lo,
+                                                                        double* __restrict__ d_hi) {
+  const int total = d_counts[0];
+  const int n = total < cap ? total : cap;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double a = pD[i], b = pD[n + i];
+  d_lo[i] = a;
+  d_hi[i] = b;
+  if (!(pst[i] == ES_PT_OK && pst[n + i] == ES_PT_OK && a * b < 0.0)) atomicAdd(d_counts + 3, 1);
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------
 int check_problem(es_context* ctx, const es_problem* prob) {
   ES_REQUIRE(ctx, prob != nullptr, "null problem");
@@ -1690,6 +1758,24 @@ int points_any(es_context* ctx, const es_problem* prob, const double* pk, const 
     default: return points_into<FAM_SLABF>(ctx, prob, pk, pw, n, pD, pst);
   }
 }
+
+// fp64 points with the count in device memory, the launch sized for n_max points
+template <int FAM>
+int points_dcount(es_context* ctx, const es_problem* prob, const double* pk, const double* pw, const int* d_n, long n_max,
+                  double* pD, uint8_t* pst) {
+  hipLaunchKernelGGL((shoot_points_dcount_kernel<FAM>), dim3((unsigned)((n_max + 255) / 256)), dim3(256), 0, ctx->stream,
+                     prob->dev, pk, pw, d_n, pD, pst);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  return ES_SUCCESS;
+}
+
+int points_dcount_any(es_context* ctx, const es_problem* prob, const double* pk, const double* pw, const int* d_n,
+                      long n_max, double* pD, uint8_t* pst) {
+  if (n_max <= 0) return ES_SUCCESS;
+#define CALL_PTS(F) points_dcount<F>(ctx, prob, pk, pw, d_n, n_max, pD, pst)
+  ES_DISPATCH_FAMILY(prob->dev.family, CALL_PTS)
+#undef CALL_PTS
+}
 }  // namespace
 
 // Step 1 of the mixed search alone: the fp32 screening march, enqueued (no read-back).
@@ -1804,6 +1890,114 @@ extern "C" int es_shoot_find_roots_screened(es_context* ctx, const es_problem* p
     return ES_ERR_SCREENING;
   }
   return total > table->capacity ? ES_ERR_CAPACITY : ES_SUCCESS;
+}
+
+// ---- steps 2 - 5 with the counts on the device (es_shoot_find_roots_screened_async / es_shoot_find_roots_mixed_async) ----
+namespace {
+// every argument check of the synchronous pair, before anything is enqueued
+int check_screened_async_args(es_context* ctx, const es_problem* prob, const double* d_k, int nk, const double* d_w,
+                              int nw, int w_mode, int n_bisect, const double* d_D, const uint8_t* d_status,
+                              const es_root_table* table, const int32_t* d_counts) {
+  int rc = check_mixed_args(ctx, prob, nk, nw, w_mode);
+  if (rc) return rc;
+  ES_REQUIRE(ctx, table && d_counts, "null pointer");
+  ES_REQUIRE(ctx, n_bisect >= 0 && table->capacity >= 0, "negative size");
+  ES_REQUIRE(ctx, table->capacity <= (1 << 30), "table capacity above 2^30 (the bracket-end count is an int32)");
+  if ((long)nk * nw == 0) return ES_SUCCESS;
+  ES_REQUIRE(ctx, d_k && d_w && d_D && d_status, "null pointer");
+  ES_REQUIRE(ctx, table->capacity == 0 || (table->d_k && table->d_w && table->d_w_lo && table->d_w_hi &&
+                                           table->d_resid && table->d_row && table->d_flag),
+             "null root table arrays");
+  return ES_SUCCESS;
+}
+
+// the launches of es_shoot_find_roots_screened with every count in d_counts (include/eigensolver_amd.h); arguments checked
+int screened_enqueue(es_context* ctx, const es_problem* prob, const double* d_k, int nk, const double* d_w, int nw,
+                     int w_mode, int n_bisect, double tol_percent, double* d_D, uint8_t* d_status,
+                     const es_root_table* table, int32_t* d_counts) {
+  const long cells = (long)nk * nw;
+  const int cap = table->capacity;
+  ES_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 4 * sizeof(int32_t), ctx->stream));
+  if (cells == 0) return ES_SUCCESS;
+  int rc = es_ensure_scan_scratch(ctx, (size_t)cells);
+  if (rc) return rc;
+  // per-point scratch for every cell (unsure points) or both ends of every record (bracket ends), whichever is more: the
+  // two uses follow each other on the stream and share the buffers (33 bytes per point, include/eigensolver_amd.h)
+  const size_t npts = (size_t)cells > 2 * (size_t)cap ? (size_t)cells : 2 * (size_t)cap;
+  auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t bd = align(npts * sizeof(double));
+  rc = es_ensure_scratch(ctx, 4 * bd + align(npts));
+  if (rc) return rc;
+  char* b = (char*)ctx->d_scratch;
+  double* pk = (double*)b;
+  double* pw = (double*)(b + bd);
+  double* pD = (double*)(b + 2 * bd);
+  long* pcell = (long*)(b + 3 * bd);
+  uint8_t* pst = (uint8_t*)(b + 4 * bd);
+  const int nblocks = (int)((cells + 255) / 256);
+  // 2. unsure points -> fp64: count to d_counts[1] (ctx->d_total is taken by the bracket scan below)
+  hipLaunchKernelGGL(unsure_flag_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_status, cells, ctx->d_masks,
+                     ctx->d_block_counts);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = es_scan_block_counts_async(ctx, nblocks);
+  if (rc) return rc;
+  ES_HIP_CHECK(ctx, hipMemcpyAsync(d_counts + 1, ctx->d_total, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  hipLaunchKernelGGL(unsure_gather_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_k, d_w, nw, w_mode, cells,
+                     ctx->d_masks, ctx->d_block_counts, pk, pw, pcell);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = points_dcount_any(ctx, prob, pk, pw, d_counts + 1, cells, pD, pst);
+  if (rc) return rc;
+  hipLaunchKernelGGL(scatter_points_dcount_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, pcell, pD, pst,
+                     d_counts + 1, d_D, d_status);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  // 3. brackets on the merged array: count to d_counts[0]
+  hipLaunchKernelGGL(bracket_flag_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_D, d_status, nw, cells,
+                     ctx->d_masks, ctx->d_block_counts);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = es_scan_block_counts_async(ctx, nblocks);
+  if (rc) return rc;
+  ES_HIP_CHECK(ctx, hipMemcpyAsync(d_counts, ctx->d_total, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  if (cap == 0) return ES_SUCCESS;
+  hipLaunchKernelGGL(bracket_emit_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_k, d_w, nw, w_mode, cells,
+                     d_D, ctx->d_masks, ctx->d_block_counts, *table, table->d_w, table->d_resid);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  // 4. both ends of the first min(count, capacity) brackets in fp64; unconfirmed brackets to d_counts[3]
+  const dim3 cap_blocks((unsigned)((cap + 255) / 256));
+  hipLaunchKernelGGL(bracket_end_points_dcount_kernel, cap_blocks, dim3(256), 0, ctx->stream, *table, d_counts, pk, pw);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = points_dcount_any(ctx, prob, pk, pw, d_counts + 2, 2 * (long)cap, pD, pst);
+  if (rc) return rc;
+  hipLaunchKernelGGL(bracket_end_values_dcount_kernel, cap_blocks, dim3(256), 0, ctx->stream, pD, pst, d_counts, cap,
+                     table->d_w, table->d_resid);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  // 5. fp64 refinement sized for the capacity, count from d_counts[0] (as es_shoot_find_roots_async)
+  return dispatch_refine(ctx, prob, *table, d_counts, cap, cap / 2, n_bisect, tol_percent);
+}
+}  // namespace
+
+extern "C" int es_shoot_find_roots_screened_async(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
+                                                  const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
+                                                  double* d_D, uint8_t* d_status, es_root_table* table,
+                                                  int32_t* d_counts) {
+  if (!ctx) return ES_ERR_INVALID_ARG;
+  int rc = check_screened_async_args(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, d_D, d_status, table, d_counts);
+  if (rc) return rc;
+  ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return screened_enqueue(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, tol_percent, d_D, d_status, table, d_counts);
+}
+
+extern "C" int es_shoot_find_roots_mixed_async(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
+                                               const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
+                                               double* d_D, uint8_t* d_status, es_root_table* table, int32_t* d_counts) {
+  if (!ctx) return ES_ERR_INVALID_ARG;
+  int rc = check_screened_async_args(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, d_D, d_status, table, d_counts);
+  if (rc) return rc;
+  ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if ((long)nk * nw > 0) {
+    rc = launch_grid_f32_any(ctx, prob, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+    if (rc) return rc;
+  }
+  return screened_enqueue(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, tol_percent, d_D, d_status, table, d_counts);
 }
 
 

@@ -2,6 +2,7 @@
 the HIP kernels through the C ABI (es_problem_create, es_shoot_eval_grid, es_shoot_eval_points,
 es_shoot_find_roots)."""
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -12,6 +13,28 @@ GEOM_CYL, GEOM_CYL_TWIST, GEOM_SLAB_DENSITY, GEOM_SLAB_FLOW = 0, 1, 2, 3
 AXIS_KINK, AXIS_SAUSAGE, AXIS_ROTATION_KINK = 0, 1, 2
 W_ABSOLUTE, W_PHASE_SPEED, W_PER_ROW = 0, 1, 2
 PT_OK, PT_LEAKY, PT_NONFINITE, PT_CONTINUUM = 0, 1, 2, 3
+
+
+class ScreenCounts(NamedTuple):
+    """The count words of find_roots_screened_async / find_roots_mixed_async, read on the host."""
+    count: int          # brackets (may exceed the table capacity)
+    unsure: int         # fp64 re-evaluations of unsure grid points
+    ends: int           # fp64 re-evaluations of bracket ends
+    violations: int     # brackets whose fp64 ends do not confirm them
+    overflow: bool      # count > capacity: only the first `capacity` brackets were written and refined
+
+
+def read_screen_counts(counts, capacity):
+    """Read the four count words once (a CUDA tensor: this is the host synchronisation the async calls leave to the
+    caller; a CPU tensor works the same).  Raises EsError, naming the failure of the synchronous call's
+    ES_ERR_SCREENING, when a bracket was not confirmed by the fp64 values at its ends."""
+    c = [int(x) for x in counts.reshape(-1)[:4].tolist()]
+    assert len(c) == 4, "counts must have four words"
+    r = ScreenCounts(c[0], c[1], c[2], c[3], c[0] > int(capacity))
+    if r.violations > 0:
+        raise _lib.EsError("libeigensolver_amd: fp32-screened bracket not confirmed in fp64 (fp32 screening: "
+                           f"{r.violations} bracket(s) not confirmed by the fp64 values at their ends)")
+    return r
 
 
 def make_desc(eq, mode, m=None):
@@ -244,3 +267,44 @@ class ShootProblem:
                 continue
             m = min(n.value, rt.capacity)
             return {key: v[:m] for key, v in t.items()}, n.value, D, st, tuple(stats)
+
+    @staticmethod
+    def _check_counts(counts):
+        import torch
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.numel() == 4 and counts.is_contiguous()
+
+    def find_roots_screened_async(self, k, w, D, st, table, counts, w_mode=W_PHASE_SPEED, n_bisect=40, tol_percent=1e-3):
+        """es_shoot_find_roots_screened_async: find_roots_screened with everything enqueued on the context's stream and
+        nothing read back.  `table` is (dict, RootTable) from alloc_root_table, `counts` a 4-element int32 CUDA tensor
+        that receives (brackets, unsure re-evaluations, bracket-end re-evaluations, unconfirmed brackets); read it with
+        read_screen_counts.  Returns the full-capacity dict of the table."""
+        import torch
+        self._check_counts(counts)
+        with torch.cuda.stream(self.ctx.torch_stream):      # temporaries are released to the context's stream
+            dk, dw = self._dev(k).reshape(-1), self._dev(w)
+            nk = dk.numel()
+            nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+            t, rt = table
+            rc = self.ctx.lib.es_shoot_find_roots_screened_async(self.ctx.handle, self.handle, _lib.ptr(dk), nk, _lib.ptr(dw),
+                                                                 nw, w_mode, int(n_bisect), float(tol_percent), _lib.ptr(D),
+                                                                 _lib.ptr(st), C.byref(rt), _lib.ptr(counts))
+        _lib.check(self.ctx.handle, rc)
+        return t
+
+    def find_roots_mixed_async(self, k, w, table, counts, w_mode=W_PHASE_SPEED, n_bisect=40, tol_percent=1e-3):
+        """es_shoot_find_roots_mixed_async: find_roots_mixed with everything enqueued on the context's stream and nothing
+        read back (see find_roots_screened_async).  Returns (full-capacity dict of the table, D, status)."""
+        import torch
+        self._check_counts(counts)
+        with torch.cuda.stream(self.ctx.torch_stream):
+            dk, dw = self._dev(k).reshape(-1), self._dev(w)
+            nk = dk.numel()
+            nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+            D = torch.empty((nk, nw), dtype=torch.float64, device=dk.device)
+            st = torch.empty((nk, nw), dtype=torch.uint8, device=dk.device)
+            t, rt = table
+            rc = self.ctx.lib.es_shoot_find_roots_mixed_async(self.ctx.handle, self.handle, _lib.ptr(dk), nk, _lib.ptr(dw),
+                                                              nw, w_mode, int(n_bisect), float(tol_percent), _lib.ptr(D),
+                                                              _lib.ptr(st), C.byref(rt), _lib.ptr(counts))
+        _lib.check(self.ctx.handle, rc)
+        return t, D, st

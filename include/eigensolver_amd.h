@@ -256,6 +256,32 @@ int es_shoot_find_roots_screened(es_context* ctx, const es_problem* prob, const 
                                  const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
                                  double* d_D, uint8_t* d_status, es_root_table* table, int* h_count, int* h_stats);
 
+/* es_shoot_find_roots_screened / es_shoot_find_roots_mixed without any host synchronisation: what the synchronous calls
+ * return through h_count / h_stats and their status goes to the caller's count words instead.
+ * d_counts: int32_t[4] in DEVICE memory, written on the context's stream:
+ *   [0] bracket count (may exceed table->capacity, exactly as the d_count of es_shoot_find_roots_async, so that
+ *       es_root_table_pack_async(ctx, table, d_counts, ...) works unchanged)
+ *   [1] fp64 re-evaluations of unsure grid points                                       (h_stats[0] of the synchronous call)
+ *   [2] fp64 re-evaluations of bracket ends = 2 min([0], capacity)                      (h_stats[1])
+ *   [3] brackets whose fp64 ends do not confirm them                                    (h_stats[2]; the synchronous call
+ *       returns ES_ERR_SCREENING)
+ * For the same inputs d_D, d_status and the root table are those of es_shoot_screen_grid + es_shoot_find_roots_screened, bit
+ * for bit (the first `capacity` records when [0] > capacity).  Every launch is sized for the grid (nk * nw) or for the
+ * table capacity and takes its count from d_counts; size the table for the data (about twice the expected count), as for
+ * es_shoot_find_roots_async.  Nothing is copied to the host and nothing is synchronised, except that a call which grows the
+ * context's scratch (the first one at a larger grid or table capacity) frees and allocates device memory, and hipFree /
+ * hipMalloc synchronise.  Scratch of the context: 33 bytes per point for max(nk * nw, 2 capacity) points, plus the
+ * bracket-scan scratch of 1/8 + 1/64 bytes per grid cell.
+ * Argument errors and ES_ERR_UNSUPPORTED (a slab with per-node sign tracking) are returned at once, as by the synchronous
+ * calls, and nothing is enqueued; ES_ERR_CAPACITY and ES_ERR_SCREENING are never returned (the caller reads [0] and [3]).
+ * nk * nw == 0 zeroes all four words.  es_shoot_find_roots_mixed_async = es_shoot_screen_grid + the screened call. */
+int es_shoot_find_roots_screened_async(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
+                                       const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
+                                       double* d_D, uint8_t* d_status, es_root_table* table, int32_t* d_counts);
+int es_shoot_find_roots_mixed_async(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
+                                    const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
+                                    double* d_D, uint8_t* d_status, es_root_table* table, int32_t* d_counts);
+
 /* Send buffer of the multi-GPU exchange (one all-gather of fixed-capacity buffers per step):
  * d_out is (cap + 1) x 6 doubles, row 0 = (count, 0, ...), rows 1 .. min(count, cap) = (k, omega, m, resid, flag,
  * global row) of the first records of `table`, the rest zero.  d_rows_global[local row] maps the rows of a k-tile to
