@@ -5,6 +5,7 @@ CPU fallback for any entry point.
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libeigensolver_amd.so")
@@ -17,6 +18,18 @@ class SlabAnalyticParams(C.Structure):
 
 class EsError(RuntimeError):
     pass
+
+
+# refinement rule of a context (enum of include/eigensolver_amd.h; Context.refine_rule)
+REFINE_SECTION, REFINE_HYBRID = 0, 1
+
+
+class RefineStats(NamedTuple):
+    """es_context_refine_stats: counts of the ES_REFINE_HYBRID searches since the last read."""
+    brackets: int       # refined by the hybrid rule (more section rounds than the rule takes before its one-lane phase)
+    kept: int           # kept by the one-lane phase
+    fallback: int       # refined by the remaining section rounds and the polish steps
+    evaluations: int    # determinant evaluations of the one-lane phase
 
 
 _lib = None
@@ -85,6 +98,23 @@ class Context:
         ms, n = C.c_double(0.0), C.c_int(0)
         check(self.handle, self.lib.es_context_grid_time(self.handle, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    @property
+    def refine_rule(self):
+        """REFINE_SECTION (default) or REFINE_HYBRID: how every root search of this context refines its brackets."""
+        r = C.c_int(0)
+        check(self.handle, self.lib.es_context_get_refine_rule(self.handle, C.byref(r)))
+        return r.value
+
+    @refine_rule.setter
+    def refine_rule(self, rule):
+        check(self.handle, self.lib.es_context_set_refine_rule(self.handle, int(rule)))
+
+    def refine_stats(self):
+        """RefineStats of the hybrid searches since the last call; synchronises the stream and zeroes the counts."""
+        h = (C.c_int64 * 4)()
+        check(self.handle, self.lib.es_context_refine_stats(self.handle, h))
+        return RefineStats(*[int(v) for v in h])
 
     def close(self):
         if getattr(self, "handle", None):
@@ -158,6 +188,9 @@ def _sig(lib):
     lib.es_context_synchronize.argtypes = [vp]
     lib.es_context_grid_timer.argtypes = [vp, i]
     lib.es_context_grid_time.argtypes = [vp, C.POINTER(d), C.POINTER(i)]
+    lib.es_context_set_refine_rule.argtypes = [vp, i]
+    lib.es_context_get_refine_rule.argtypes = [vp, C.POINTER(i)]
+    lib.es_context_refine_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     # (1) closed-form slab
     P = C.POINTER(SlabAnalyticParams)
     lib.es_slab_analytic_eval.argtypes = [vp, P, i, vp, i, vp, i, vp]

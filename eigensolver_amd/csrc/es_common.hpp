@@ -28,6 +28,13 @@ struct es_context {
   // es_context_grid_timer: event pairs around the launches of the dominant (grid march) kernels on this stream
   bool timer_on = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> timer_events;
+  // es_context_set_refine_rule: ES_REFINE_SECTION / ES_REFINE_HYBRID, read by every root search at its refinement step
+  int refine_rule = ES_REFINE_SECTION;
+  // ES_REFINE_HYBRID: state of the one-lane phase, fallback root table, its index list, scan words and the fallback count,
+  // all sized by the table capacity of the call (grown on demand, never shrunk; its own buffer because the screened
+  // searches still hold pointers into d_scratch when they reach the refinement)
+  void* d_hybrid = nullptr;        size_t hybrid_cap = 0;
+  unsigned long long* d_refine_stats = nullptr;               // es_context_refine_stats: four device words
 };
 
 // Bracket a launch of a grid-march kernel with HIP events on the context's stream (no-ops unless the timer is on).
@@ -53,6 +60,12 @@ void es_timer_end(es_context* ctx);
 
 // Grow ctx->d_scratch to at least `bytes` (synchronises the stream before freeing the old buffer).
 int es_ensure_scratch(es_context* ctx, size_t bytes);
+
+// Grow ctx->d_hybrid to at least `bytes`, as es_ensure_scratch grows d_scratch.
+int es_ensure_hybrid_scratch(es_context* ctx, size_t bytes);
+
+// Exclusive scan of `nblocks` per-block counts in place, total to *d_total_out; enqueued.
+int es_scan_counts_async(es_context* ctx, int* d_counts, int nblocks, int* d_total_out);
 
 // Grow the compaction scratch so that `cells` cells fit.
 int es_ensure_scan_scratch(es_context* ctx, size_t cells);

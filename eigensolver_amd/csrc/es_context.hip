@@ -42,6 +42,11 @@ extern "C" int es_context_create(int device, void* stream, es_context** out) {
   if (hipSetDevice(device) != hipSuccess) { delete ctx; return ES_ERR_HIP; }
   if (hipMalloc(&ctx->d_total, sizeof(int)) != hipSuccess) { delete ctx; return ES_ERR_HIP; }
   if (hipHostMalloc(&ctx->h_total, sizeof(int)) != hipSuccess) { (void)hipFree(ctx->d_total); delete ctx; return ES_ERR_HIP; }
+  if (hipMalloc(&ctx->d_refine_stats, 4 * sizeof(unsigned long long)) != hipSuccess ||
+      hipMemset(ctx->d_refine_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess) {
+    if (ctx->d_refine_stats) (void)hipFree(ctx->d_refine_stats);
+    (void)hipFree(ctx->d_total); (void)hipHostFree(ctx->h_total); delete ctx; return ES_ERR_HIP;
+  }
   *out = ctx;
   return ES_SUCCESS;
 }
@@ -54,6 +59,8 @@ extern "C" int es_context_destroy(es_context* ctx) {
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->d_cols) (void)hipFree(ctx->d_cols);
   if (ctx->d_coldead) (void)hipFree(ctx->d_coldead);
+  if (ctx->d_hybrid) (void)hipFree(ctx->d_hybrid);
+  if (ctx->d_refine_stats) (void)hipFree(ctx->d_refine_stats);
   if (ctx->d_total) (void)hipFree(ctx->d_total);
   if (ctx->h_total) (void)hipHostFree(ctx->h_total);
   for (auto& e : ctx->timer_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -99,6 +106,31 @@ extern "C" int es_context_grid_time(es_context* ctx, double* h_total_ms, int* h_
   return ES_SUCCESS;
 }
 
+extern "C" int es_context_set_refine_rule(es_context* ctx, int rule) {
+  if (!ctx) return ES_ERR_INVALID_ARG;
+  ES_REQUIRE(ctx, rule == ES_REFINE_SECTION || rule == ES_REFINE_HYBRID, "unknown refine rule");
+  ctx->refine_rule = rule;
+  return ES_SUCCESS;
+}
+
+extern "C" int es_context_get_refine_rule(const es_context* ctx, int* h_rule) {
+  if (!ctx || !h_rule) return ES_ERR_INVALID_ARG;
+  *h_rule = ctx->refine_rule;
+  return ES_SUCCESS;
+}
+
+extern "C" int es_context_refine_stats(es_context* ctx, int64_t h[4]) {
+  if (!ctx) return ES_ERR_INVALID_ARG;
+  ES_REQUIRE(ctx, h, "null pointer");
+  ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  unsigned long long v[4];
+  ES_HIP_CHECK(ctx, hipMemcpyAsync(v, ctx->d_refine_stats, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
+  ES_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_refine_stats, 0, sizeof(v), ctx->stream));
+  ES_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < 4; ++i) h[i] = (int64_t)v[i];
+  return ES_SUCCESS;
+}
+
 extern "C" const char* es_last_error(const es_context* ctx) { return ctx ? ctx->last_error.c_str() : ""; }
 
 extern "C" int es_context_synchronize(es_context* ctx) {
@@ -119,6 +151,21 @@ int es_ensure_scratch(es_context* ctx, size_t bytes) {
   const size_t cap = bytes + bytes / 4;                          // head room: batches of a sweep grow slowly
   ES_HIP_CHECK(ctx, hipMalloc(&ctx->d_scratch, cap));
   ctx->scratch_cap = cap;
+  return ES_SUCCESS;
+}
+
+int es_ensure_hybrid_scratch(es_context* ctx, size_t bytes) {
+  if (bytes <= ctx->hybrid_cap) return ES_SUCCESS;
+  ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (ctx->d_hybrid) {
+    ES_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));        // earlier calls may still read the old buffer
+    ES_HIP_CHECK(ctx, hipFree(ctx->d_hybrid));
+    ctx->d_hybrid = nullptr;
+    ctx->hybrid_cap = 0;
+  }
+  const size_t cap = bytes + bytes / 4;
+  ES_HIP_CHECK(ctx, hipMalloc(&ctx->d_hybrid, cap));
+  ctx->hybrid_cap = cap;
   return ES_SUCCESS;
 }
 
@@ -177,10 +224,14 @@ __global__ __launch_bounds__(1024) void es_block_scan_kernel(int* __restrict__ c
   if (tid == 0) *total = carry;
 }
 
-int es_scan_block_counts_async(es_context* ctx, int nblocks) {
-  hipLaunchKernelGGL(es_block_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->d_block_counts, nblocks, ctx->d_total);
+int es_scan_counts_async(es_context* ctx, int* d_counts, int nblocks, int* d_total_out) {
+  hipLaunchKernelGGL(es_block_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_counts, nblocks, d_total_out);
   ES_HIP_CHECK(ctx, hipGetLastError());
   return ES_SUCCESS;
+}
+
+int es_scan_block_counts_async(es_context* ctx, int nblocks) {
+  return es_scan_counts_async(ctx, ctx->d_block_counts, nblocks, ctx->d_total);
 }
 
 int es_scan_block_counts(es_context* ctx, int nblocks, int* h_total_out) {

@@ -387,6 +387,153 @@ void refine_polish_kernel(ShootDev P, es_root_table tab, double* d_lo, double* d
   }
 }
 
+// ---- ES_REFINE_HYBRID (include/eigensolver_amd.h): S section rounds, one lane per bracket, section rule as the fallback --
+// All three constants are part of the rule, which is fixed per bracket (see kRefineSections): tests/refine_hybrid_model.py
+// restates them.
+constexpr int kHybridSections = 1;          // S: 17-section rounds before the one-lane phase (1 or 2)
+constexpr int kHybridSteps = 8;             // M: evaluations of the one-lane phase at most
+constexpr double kHybridEps = 1e-12;        // relative step / width at which an iterate counts as converged
+
+// State of the one-lane phase between its launches; `info`: bits 0-1 the end the last step retained (1 lower, 2 upper,
+// 0 none yet), bits 2-3 HYB_ACTIVE / HYB_KEPT / HYB_FAILED (the fallback takes every bracket that is not HYB_KEPT).
+struct HybridState {
+  double* lo; double* hi; double* flo; double* fhi; double* xprev;
+  int* info;
+};
+constexpr int HYB_ACTIVE = 0, HYB_KEPT = 1, HYB_FAILED = 2;
+
+// One lane per bracket, modelled on refine_polish_kernel<FAM, true>: one inlined evaluation site, count from device memory,
+// launch sized for the capacity, ONE step per launch (`step` = 0 .. kHybridSteps - 1) with the state in S.  A loop over the
+// steps inside the kernel was built for every family and dropped: the compiler hoists the step-invariant values of the
+// inlined march out of it (see refine_kernel), about 50 more VGPRs for the cylinder families, and every looped form, the
+// slabs' included, had a private segment of 36 - 100 bytes per lane; the one-step form has none.  A bracket still
+// HYB_ACTIVE after the last step is simply not kept.
+// Step 0 reads the state the section rounds left in the table columns (d_lo / d_hi = D at the ends); a table row is written
+// ONLY for a bracket the phase keeps: every other row still holds that state when the fallback gathers it.
+// "Still iterating" is voted over the WORKGROUP, not the wave (__syncthreads_or): shoot_point stages the base table with all
+// threads of the workgroup between barriers, so a wave may not stay out of an evaluation alone; a workgroup whose brackets
+// are all finished returns at once.  stats: es_context_refine_stats.
+template <int FAM, int WPE = (FAM == FAM_CYL0 ? 3 : 2)>
+__global__ __launch_bounds__(64 * REFINE_WAVES) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
+void refine_superlinear_kernel(ShootDev P, es_root_table tab, const double* d_lo, const double* d_hi, HybridState S,
+                               const int* __restrict__ d_n, int n_max, int step, double tol_percent,
+                               unsigned long long* stats) {
+  ES_POINT_LDS(FAM);
+  const int n = d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+  if ((int)(blockIdx.x * (64 * REFINE_WAVES)) >= n) return;                               // workgroup-uniform
+  const int i = blockIdx.x * (64 * REFINE_WAVES) + (int)threadIdx.x;
+  const bool in = i < n;
+  const bool first = step == 0;
+  const int info = (in && !first) ? S.info[i] : 0;
+  const bool active = in && ((info >> 2) == HYB_ACTIVE);
+  if (!__syncthreads_or(active ? 1 : 0)) return;                                          // workgroup-uniform
+  const double k = in ? tab.d_k[i] : 1.0;
+  double lo, hi, flo, fhi, xprev;
+  if (first) {
+    lo = in ? tab.d_w_lo[i] : 1.0;
+    hi = in ? tab.d_w_hi[i] : 2.0;
+    flo = in ? d_lo[i] : 1.0;
+    fhi = in ? d_hi[i] : -1.0;
+    xprev = NAN;
+  } else {
+    lo = active ? S.lo[i] : 1.0;
+    hi = active ? S.hi[i] : 2.0;
+    flo = active ? S.flo[i] : 1.0;
+    fhi = active ? S.fhi[i] : -1.0;
+    xprev = active ? S.xprev[i] : NAN;
+  }
+  int side = info & 3, status = info >> 2;
+  double D = 0.0, rel = 0.0; uint8_t st = 0;
+  double x = lo - flo * (hi - lo) / (fhi - flo);
+  if (!(x > lo && x < hi)) x = lo + (hi - lo) * 0.5;                                      // NaN included
+  shoot_point<FAM>(P, k, x, x, D, rel, st, es_point_lds);
+  if (active) {
+    if (D == D) {
+      // Illinois: an end retained twice in a row has its value halved (the sign, which is all the bracket needs, stays)
+      if (D * flo < 0.0) { hi = x; fhi = D; if (side == 1) flo *= 0.5; side = 1; }
+      else { lo = x; flo = D; if (side == 2) fhi *= 0.5; side = 2; }
+      const double ax = fabs(x);
+      if (D == 0.0 || fabs(x - xprev) <= kHybridEps * ax || (hi - lo) <= kHybridEps * ax)
+        status = (st == ES_PT_OK && rel < tol_percent) ? HYB_KEPT : HYB_FAILED;           // classified at the iterate that met the test
+    } else {
+      status = HYB_FAILED;
+    }
+    if (status == HYB_KEPT) {
+      tab.d_w_lo[i] = lo;
+      tab.d_w_hi[i] = hi;
+      tab.d_w[i] = x;
+      tab.d_resid[i] = rel;
+      tab.d_flag[i] = 1;
+    } else if (status == HYB_ACTIVE) {
+      S.lo[i] = lo; S.hi[i] = hi; S.flo[i] = flo; S.fhi[i] = fhi; S.xprev[i] = x;
+    }
+    S.info[i] = side | (status << 2);
+  }
+  const int n_eval = __popcll(__ballot(active)), n_kept = __popcll(__ballot(active && status == HYB_KEPT));
+  if ((threadIdx.x & 63) == 0) {
+    if (first && n_eval) atomicAdd(stats + 0, (unsigned long long)n_eval);               // step 0: every bracket is active
+    if (n_kept) atomicAdd(stats + 1, (unsigned long long)n_kept);
+    if (n_eval) atomicAdd(stats + 3, (unsigned long long)n_eval);
+  }
+}
+
+// Fallback of the hybrid rule: the brackets the one-lane phase did not keep, in order.  Flags as 64-bit ballots and counts
+// per 256 brackets over the whole launch (sized for the capacity: blocks behind the count write zeros, the scan reads them).
+__global__ __launch_bounds__(256) void hybrid_flag_kernel(const int* __restrict__ info, const int* __restrict__ d_n,
+                                                          int n_max, uint64_t* __restrict__ masks,
+                                                          int* __restrict__ block_counts, unsigned long long* stats) {
+  __shared__ int wave_cnt[4];
+  const int n = d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  const bool flag = i < n && (info[i] >> 2) != HYB_KEPT;
+  const uint64_t m = __ballot(flag);
+  if ((threadIdx.x & 63) == 0) {
+    masks[i >> 6] = m;
+    wave_cnt[threadIdx.x >> 6] = __popcll(m);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int c = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    block_counts[blockIdx.x] = c;
+    if (c) atomicAdd(stats + 2, (unsigned long long)c);
+  }
+}
+
+// row `pos` of the fallback table = bracket idx[pos] with the state the section rounds left in its row
+__global__ __launch_bounds__(256) void hybrid_gather_kernel(es_root_table tab, es_root_table ftab, int* __restrict__ idx,
+                                                            const uint64_t* __restrict__ masks,
+                                                            const int* __restrict__ block_off,
+                                                            const int* __restrict__ d_n, int n_max) {
+  const int n = d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= n) return;
+  if (!((masks[i >> 6] >> (i & 63)) & 1ull)) return;
+  const int pos = es_cell_rank(masks, block_off, (long)i);
+  if (pos >= ftab.capacity) return;
+  ftab.d_k[pos] = tab.d_k[i];
+  ftab.d_w_lo[pos] = tab.d_w_lo[i];
+  ftab.d_w_hi[pos] = tab.d_w_hi[i];
+  ftab.d_w[pos] = tab.d_w[i];                                                             // D at the lower end
+  ftab.d_resid[pos] = tab.d_resid[i];                                                     // D at the upper end
+  ftab.d_row[pos] = tab.d_row[i];
+  idx[pos] = i;
+}
+
+__global__ __launch_bounds__(256) void hybrid_scatter_kernel(es_root_table ftab, es_root_table tab,
+                                                             const int* __restrict__ idx,
+                                                             const int* __restrict__ d_nf, int n_max) {
+  const int nf = *d_nf < n_max ? *d_nf : n_max;
+  const int j = blockIdx.x * 256 + (int)threadIdx.x;
+  if (j >= nf) return;
+  const int i = idx[j];
+  if (i < 0 || i >= tab.capacity) return;
+  tab.d_w[i] = ftab.d_w[j];
+  tab.d_w_lo[i] = ftab.d_w_lo[j];
+  tab.d_w_hi[i] = ftab.d_w_hi[j];
+  tab.d_resid[i] = ftab.d_resid[j];
+  tab.d_flag[i] = ftab.d_flag[j];
+}
+
 // =====================================================================================================================
 // fp32 screening of the (k, omega) grid (BASELINE.json configs[4]: "fp32 bracket + fp64 refine").
 //
@@ -1204,21 +1351,13 @@ int launch_points(es_context* ctx, const es_problem* prob, const double* d_k, co
 }
 
 // d_n: bracket count in device memory (nullptr: n_max IS the count); n_max: launch bound (count known on the host, or the
-// table capacity); n_hint: what the count is expected to be (selects between variants that give identical results)
+// table capacity); n_hint: what the count is expected to be (selects between variants that give identical results).
+// `rounds` section rounds (np < 0: sections only, D at the ends stays in d_lo / d_hi), then, if `polish`, the polish steps:
+// the section rule is one call with all its rounds; the hybrid rule splits the same launches in two calls around its
+// one-lane phase (the state between two section rounds is the four doubles per bracket in the table either way).
 template <int FAM>
-int launch_refine(es_context* ctx, const es_problem* prob, const es_root_table& tab, double* d_lo, double* d_hi,
-                  const int* d_n, int n_max, int n_hint, int n_bisect, double tol) {
-  // (LANES+1)-section rounds equivalent to n_bisect halvings: (LANES+1)^R >= 2^n_bisect
-  int sections = kRefineSections;
-  if (const char* ev = getenv("ES_REFINE_SECTIONS")) {            // tuning aid, honoured by the port as well: 5, 9 or 17
-    const int v = atoi(ev);
-    if (v == 5 || v == 9 || v == 17) sections = v;
-  }
-  int rounds = 0;
-  for (double span = 1.0, need = ldexp(1.0, n_bisect < 1000 ? n_bisect : 1000); span < need; span *= (double)sections) ++rounds;
-  // section rounds with LANES lanes per bracket, then the polish steps with one lane per bracket (d_lo / d_hi carry D at
-  // the ends of the narrowed bracket from one kernel to the other)
-  const int np = (ES_REFINE_POLISH > 0 && rounds > 0) ? -1 : ES_REFINE_POLISH;
+int launch_refine_steps(es_context* ctx, const es_problem* prob, const es_root_table& tab, double* d_lo, double* d_hi,
+                        const int* d_n, int n_max, int n_hint, int sections, int rounds, int np, bool polish, double tol) {
   // 17-section of the untwisted cylinder with np < 0 (sections only): node entries shared inside the wave, 32 steps per
   // chunk (14.6 KB of LDS per wave).  Bit-identical to the per-lane entries, so the choice could follow the bracket count
   // (ES_REFINE_SHARED_MIN); measured in round 3 with the count on the device (same box, tile of an E-GPU run, ms per
@@ -1260,7 +1399,7 @@ int launch_refine(es_context* ctx, const es_problem* prob, const es_root_table& 
   }
 #undef ES_REFINE
   ES_HIP_CHECK(ctx, hipGetLastError());
-  if (np < 0) {
+  if (np < 0 && polish) {
     if (one_round) {
       if constexpr (ONE_ROUND_FAM) {
         for (int p_ = 0; p_ < ES_REFINE_POLISH; ++p_)
@@ -1273,6 +1412,98 @@ int launch_refine(es_context* ctx, const es_problem* prob, const es_root_table& 
     ES_HIP_CHECK(ctx, hipGetLastError());
   }
   return ES_SUCCESS;
+}
+
+// ES_REFINE_SECTIONS in the environment (tuning aid, honoured by the port as well): 5, 9 or 17
+int refine_sections() {
+  int sections = kRefineSections;
+  if (const char* ev = getenv("ES_REFINE_SECTIONS")) {
+    const int v = atoi(ev);
+    if (v == 5 || v == 9 || v == 17) sections = v;
+  }
+  return sections;
+}
+
+// the hybrid rule is defined on 17-section only; checked by every search before it enqueues anything
+int check_refine_rule(es_context* ctx) {
+  if (ctx->refine_rule == ES_REFINE_HYBRID && refine_sections() != kRefineSections) {
+    ctx->last_error = "ES_REFINE_HYBRID is defined for 17-section only (ES_REFINE_SECTIONS is set to another rule)";
+    return ES_ERR_UNSUPPORTED;
+  }
+  return ES_SUCCESS;
+}
+
+// ES_REFINE_HYBRID with more rounds than kHybridSections (include/eigensolver_amd.h).  Everything is enqueued and sized for
+// n_max; the number of fallback brackets never leaves the device.
+template <int FAM>
+int launch_refine_hybrid(es_context* ctx, const es_problem* prob, const es_root_table& tab, const int* d_n, int n_max,
+                         int n_hint, int rounds, double tol) {
+  if (n_max <= 0) return ES_SUCCESS;
+  // carve the context's hybrid buffer: one-lane state, fallback table, index list, scan words, fallback count
+  auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t cap = (size_t)n_max;
+  const size_t bd = align(cap * sizeof(double)), bi = align(cap * sizeof(int)), bf = align(cap);
+  const int nblk = (n_max + 255) / 256;
+  const size_t bm = align((size_t)nblk * 4 * sizeof(uint64_t)), bc = align((size_t)(nblk + 1) * sizeof(int));
+  int rc = es_ensure_hybrid_scratch(ctx, 10 * bd + 3 * bi + bf + bm + bc + 256);
+  if (rc) return rc;
+  char* b = (char*)ctx->d_hybrid;
+  auto take = [&](size_t bytes) { char* p = b; b += bytes; return p; };
+  HybridState S;
+  S.lo = (double*)take(bd); S.hi = (double*)take(bd); S.flo = (double*)take(bd); S.fhi = (double*)take(bd);
+  S.xprev = (double*)take(bd);
+  S.info = (int*)take(bi);
+  es_root_table ftab;
+  ftab.d_k = (double*)take(bd); ftab.d_w = (double*)take(bd); ftab.d_w_lo = (double*)take(bd);
+  ftab.d_w_hi = (double*)take(bd); ftab.d_resid = (double*)take(bd);
+  ftab.d_row = (int32_t*)take(bi); ftab.d_flag = (uint8_t*)take(bf);
+  ftab.capacity = n_max;
+  int* idx = (int*)take(bi);
+  uint64_t* masks = (uint64_t*)take(bm);
+  int* counts = (int*)take(bc);
+  int* d_nf = (int*)take(256);
+  // 1. S section rounds, the launches of the section rule
+  rc = launch_refine_steps<FAM>(ctx, prob, tab, tab.d_w, tab.d_resid, d_n, n_max, n_hint, kRefineSections, kHybridSections,
+                                -1, false, tol);
+  if (rc) return rc;
+  // 2. one lane per bracket, one step per launch
+  const dim3 wg(64 * REFINE_WAVES), grid((n_max + 64 * REFINE_WAVES - 1) / (64 * REFINE_WAVES));
+  for (int s_ = 0; s_ < kHybridSteps; ++s_)
+    hipLaunchKernelGGL((refine_superlinear_kernel<FAM>), grid, wg, 0, ctx->stream, prob->dev, tab, tab.d_w, tab.d_resid, S,
+                       d_n, n_max, s_, tol, ctx->d_refine_stats);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  // 3. fallback: gather in order, the remaining rounds and the polish steps on the scratch table, scatter back
+  hipLaunchKernelGGL(hybrid_flag_kernel, dim3(nblk), dim3(256), 0, ctx->stream, S.info, d_n, n_max, masks, counts,
+                     ctx->d_refine_stats);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = es_scan_counts_async(ctx, counts, nblk, d_nf);
+  if (rc) return rc;
+  hipLaunchKernelGGL(hybrid_gather_kernel, dim3(nblk), dim3(256), 0, ctx->stream, tab, ftab, idx, masks, counts, d_n, n_max);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = launch_refine_steps<FAM>(ctx, prob, ftab, ftab.d_w, ftab.d_resid, d_nf, n_max, n_hint, kRefineSections,
+                                rounds - kHybridSections, -1, true, tol);
+  if (rc) return rc;
+  hipLaunchKernelGGL(hybrid_scatter_kernel, dim3(nblk), dim3(256), 0, ctx->stream, ftab, tab, idx, d_nf, n_max);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  return ES_SUCCESS;
+}
+
+template <int FAM>
+int launch_refine(es_context* ctx, const es_problem* prob, const es_root_table& tab, double* d_lo, double* d_hi,
+                  const int* d_n, int n_max, int n_hint, int n_bisect, double tol) {
+  // (LANES+1)-section rounds equivalent to n_bisect halvings: (LANES+1)^R >= 2^n_bisect
+  const int sections = refine_sections();
+  int rounds = 0;
+  for (double span = 1.0, need = ldexp(1.0, n_bisect < 1000 ? n_bisect : 1000); span < need; span *= (double)sections) ++rounds;
+  if (ctx->refine_rule == ES_REFINE_HYBRID) {
+    const int rc = check_refine_rule(ctx);
+    if (rc) return rc;
+    if (rounds > kHybridSections) return launch_refine_hybrid<FAM>(ctx, prob, tab, d_n, n_max, n_hint, rounds, tol);
+  }
+  // section rounds with LANES lanes per bracket, then the polish steps with one lane per bracket (d_lo / d_hi carry D at
+  // the ends of the narrowed bracket from one kernel to the other)
+  const int np = (ES_REFINE_POLISH > 0 && rounds > 0) ? -1 : ES_REFINE_POLISH;
+  return launch_refine_steps<FAM>(ctx, prob, tab, d_lo, d_hi, d_n, n_max, n_hint, sections, rounds, np, true, tol);
 }
 
 int dispatch_refine(es_context* ctx, const es_problem* prob, const es_root_table& tab, const int* d_n, int n_max, int n_hint,
@@ -1571,6 +1802,8 @@ int check_find_roots_args(es_context* ctx, const es_problem* prob, int nk, int n
                           const es_root_table* table) {
   int rc = check_problem(ctx, prob);
   if (rc) return rc;
+  rc = check_refine_rule(ctx);
+  if (rc) return rc;
   ES_REQUIRE(ctx, table, "null pointer");
   ES_REQUIRE(ctx, nk >= 0 && nw >= 0 && n_bisect >= 0 && table->capacity >= 0, "negative size");
   ES_REQUIRE(ctx, w_mode >= 0 && w_mode <= 2, "w_mode");
@@ -1808,6 +2041,8 @@ extern "C" int es_shoot_find_roots_screened(es_context* ctx, const es_problem* p
   if (!ctx) return ES_ERR_INVALID_ARG;
   int rc = check_mixed_args(ctx, prob, nk, nw, w_mode);
   if (rc) return rc;
+  rc = check_refine_rule(ctx);
+  if (rc) return rc;
   ES_REQUIRE(ctx, table && h_count, "null pointer");
   ES_REQUIRE(ctx, n_bisect >= 0 && table->capacity >= 0, "negative size");
   *h_count = 0;
@@ -1899,6 +2134,8 @@ int check_screened_async_args(es_context* ctx, const es_problem* prob, const dou
                               int nw, int w_mode, int n_bisect, const double* d_D, const uint8_t* d_status,
                               const es_root_table* table, const int32_t* d_counts) {
   int rc = check_mixed_args(ctx, prob, nk, nw, w_mode);
+  if (rc) return rc;
+  rc = check_refine_rule(ctx);
   if (rc) return rc;
   ES_REQUIRE(ctx, table && d_counts, "null pointer");
   ES_REQUIRE(ctx, n_bisect >= 0 && table->capacity >= 0, "negative size");

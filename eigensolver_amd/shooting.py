@@ -13,6 +13,8 @@ GEOM_CYL, GEOM_CYL_TWIST, GEOM_SLAB_DENSITY, GEOM_SLAB_FLOW = 0, 1, 2, 3
 AXIS_KINK, AXIS_SAUSAGE, AXIS_ROTATION_KINK = 0, 1, 2
 W_ABSOLUTE, W_PHASE_SPEED, W_PER_ROW = 0, 1, 2
 PT_OK, PT_LEAKY, PT_NONFINITE, PT_CONTINUUM = 0, 1, 2, 3
+# refinement rule of the context every search below picks up (Context.refine_rule, Context.refine_stats)
+from ._lib import REFINE_SECTION, REFINE_HYBRID, RefineStats  # noqa: E402,F401
 
 
 class ScreenCounts(NamedTuple):

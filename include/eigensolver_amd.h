@@ -282,6 +282,43 @@ int es_shoot_find_roots_mixed_async(es_context* ctx, const es_problem* prob, con
                                     const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
                                     double* d_D, uint8_t* d_status, es_root_table* table, int32_t* d_counts);
 
+/* Refinement rule of the context, read by all six searches above at their refinement step (signatures unchanged).
+ *   ES_REFINE_SECTION (default): the rule described at es_shoot_find_roots, R = ceil(n_bisect ln 2 / ln 17) rounds of
+ *     17-section and two regula-falsi steps: 16 R + 2 marches per bracket.
+ *   ES_REFINE_HYBRID: fixed per bracket like the section rule (nothing in it depends on the bracket count of the call, so a
+ *     tiled grid still gives the one-call table).  With S = 1 (kHybridSections):
+ *       R <= S: the section rule itself, same launches, same table bit for bit.
+ *       otherwise 1. S rounds of 17-section, by the same kernels;
+ *                 2. one lane per bracket, at most 8 evaluations of a bracketing secant iteration with Illinois scaling (an
+ *                    end retained twice in a row has its D halved); an iterate not strictly inside the bracket is replaced by
+ *                    the mid-point; a NaN evaluation ends the phase for the bracket.  Converged: D == 0, or |step| <= 1e-12
+ *                    |omega|, or bracket width <= 1e-12 |omega| (independent of n_bisect).  The bracket is KEPT iff converged,
+ *                    ES_PT_OK and rel < tol_percent at that iterate: d_w is the iterate that met the test, d_resid its rel,
+ *                    [d_w_lo, d_w_hi] the final sign-change bracket (ends inclusive), d_flag = 1;
+ *                 3. every bracket not kept is gathered, in order, with the state step 1 left, into a scratch root table, the
+ *                    remaining R - S rounds and the two regula-falsi steps run on that table by the same kernels, and the
+ *                    rows are scattered back.
+ *     What is GUARANTEED: every row with d_flag = 0 and every row that took step 3 is the ES_REFINE_SECTION row, bit for
+ *     bit; d_row, d_k and the count are those of the section rule; d_flag is >= the section rule's.  What is EMPIRICAL: that
+ *     a root kept by step 2 is the sign change nearest the lower end of the bracket, i.e. the root the section rule
+ *     converges to (a bracketing secant iteration may settle on another sign change of the bracket); on the fourteen
+ *     test problems every kept root is within 1e-12 relative of the section rule's converged root (n_bisect = 44) and no
+ *     kept bracket is one the converged section table rejects (tests/test_refine_hybrid_host.py, tests/refine_hybrid_model.py).
+ *     With ES_REFINE_SECTIONS in the environment set to 5 or 9 the searches return ES_ERR_UNSUPPORTED under this rule.
+ *     The asynchronous searches stay free of read-backs: every launch is sized for the table capacity and the number of
+ *     brackets in step 3 is a device word; the context holds 93 more bytes per table entry of capacity (grown, with
+ *     a quarter of head room, as the scratch of es_shoot_find_roots_screened_async is: the first call at a larger capacity
+ *     frees and allocates device memory, which synchronises).
+ * es_context_set_refine_rule: an unknown rule returns ES_ERR_INVALID_ARG and changes nothing.
+ * es_context_refine_stats synchronises the stream, returns four counts summed over the searches since the last call and
+ * zeroes them (as es_context_grid_time): h[0] brackets refined by steps 1 - 3 of the hybrid rule, h[1] kept by step 2,
+ * h[2] sent to step 3 (h[1] + h[2] = h[0]), h[3] evaluations of step 2.  Marches per bracket =
+ * 16 S + h[3] / h[0] + (16 (R - S) + 2) h[2] / h[0]. */
+enum { ES_REFINE_SECTION = 0, ES_REFINE_HYBRID = 1 };
+int es_context_set_refine_rule(es_context* ctx, int rule);
+int es_context_get_refine_rule(const es_context* ctx, int* h_rule);
+int es_context_refine_stats(es_context* ctx, int64_t h[4]);
+
 /* Send buffer of the multi-GPU exchange (one all-gather of fixed-capacity buffers per step):
  * d_out is (cap + 1) x 6 doubles, row 0 = (count, 0, ...), rows 1 .. min(count, cap) = (k, omega, m, resid, flag,
  * global row) of the first records of `table`, the rest zero.  d_rows_global[local row] maps the rows of a k-tile to
