@@ -19,6 +19,10 @@ LIB = os.path.join(LIBDIR, "libeigensolver_amd.so")
 # computes, so the interior march is bit-identical to oracle/c/shoot_port.c (tests/test_shoot_gpu.py); never loaded by
 # the product path
 LIB_IEEE = os.path.join(LIBDIR, "libeigensolver_amd_ieee.so")
+# test-only probe of the device math header (tests/devmath/devmath_probe.hip: one Bessel evaluation per thread, measured
+# against correctly rounded values by tests/test_devmath_gpu.py); same flags as the library, never loaded by the package
+PROBE_SRC = os.path.join(os.path.dirname(HERE), "tests", "devmath", "devmath_probe.hip")
+LIB_PROBE = os.path.join(LIBDIR, "libes_devmath_probe.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
@@ -72,6 +76,24 @@ def _compile_and_link(lib, extra_flags, tag, verbose):
     return lib
 
 
+def _probe_needs_build():
+    if not os.path.exists(LIB_PROBE):
+        return True
+    t = os.path.getmtime(LIB_PROBE)
+    return any(os.path.getmtime(s) > t for s in (PROBE_SRC, os.path.join(CSRC, "es_bessel.hpp")))
+
+
+def _build_probe(verbose):
+    cmd = [_hipcc()] + FLAGS + ["-shared", PROBE_SRC, "-o", LIB_PROBE]
+    if verbose:
+        print(" ".join(cmd))
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc failed for {PROBE_SRC}:\n{r.stdout}")
+    if verbose and r.stdout.strip():
+        print(r.stdout)
+
+
 def build(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     # ES_BUILD_ALL_SHAPES=1: the measuring build of tools/probe/time_grid_shapes.py -- every (points per lane, waves per
@@ -82,6 +104,8 @@ def build(force=False, verbose=False):
         _compile_and_link(LIB, extra, "", verbose)
     if force or needs_build(LIB_IEEE):
         _compile_and_link(LIB_IEEE, ["-DES_IEEE_DIVISION"], ".ieee", verbose)
+    if os.path.exists(PROBE_SRC) and (force or _probe_needs_build()):      # a source tree with its tests
+        _build_probe(verbose)
     return LIB
 
 

@@ -8,7 +8,16 @@
 //                then the upward recurrence K_{n+1} = K_{n-1} + (2n/x) K_n (stable).
 //   * I_n, I_{n+1}: ascending power series (all terms positive, no cancellation); only called for x < ~50
 //                where the I-admixture of the far-field initial values is not below rounding.
-// Accuracy (tests/test_hostmath.py, against scipy.special.kve / ive): <= 4e-16 relative on x in [1e-6, 700].
+// Accuracy, host build against correctly rounded values (tests/golden/bessel_truth.npz, mpmath at 40 digits; orders 0 ... 40,
+// tests/test_hostmath.py::test_truth; u = 2^-52 = 2.2e-16), worst relative error:
+//   e^x K_n, K_{n+1}    x in [1e-6, 700]: 12 u (2.6e-15) at n = 0, 12.5 u at n = 11, 17 u at n = 20, 26 u (5.7e-15) at n = 40.
+//                       The worst lies just below x = 2, where the ascending series of K_0 subtracts terms 12 times the
+//                       result; x <= 1: 2 u (n = 0) ... 7 u (n = 11); x > 2: 1.1 u (n = 0), 1.8 u (n <= 5), 5 u (n = 11)
+//   e^-x I_n, I_{n+1}   series, x <= 60: 12 u (2.7e-15), at x = 47.5; x <= 20: 6 u
+//                       from K (ie_pair_from_k), x in [1e-6, 700]: 15 u (3.3e-15) for n <= 11, 28 u (6.2e-15) at n = 40
+//   J_n, Y_n            x in [1e-5, 80]: 33 u (7.4e-15) of the envelope hypot(J_n, Y_n), at x = 63; x <= 20: 21 u
+// The device build (qdiv, device log / exp / sqrt) is held to these figures plus one u per operation that differs from the
+// host's by tests/test_devmath_gpu.py, which records what it measures.
 #pragma once
 #include <math.h>
 
@@ -77,7 +86,7 @@ constexpr double kPi = 3.14159265358979323846264338327950288;
 
 // sqrt(x) e^x K_0(x) and sqrt(x) e^x K_1(x) on x >= 2 as Chebyshev series in y = 4/x - 1 (25 terms: the 26th is below 2e-18;
 // coefficients by interpolation at 96 Chebyshev nodes in 50-digit arithmetic, mpmath).  Evaluated by Clenshaw's recurrence
-// the pair is within 2.8e-16 of the true values on [2, 700] (tests/test_hostmath.py against scipy.special.kve) at about
+// the pair is within 1.1 u = 2.4e-16 of the true values on (2, 700] (tests/test_hostmath.py::test_truth, order 0) at about
 // 110 instructions, where Steed's CF2 needed 10 ... 40 iterations of 25 instructions and a reciprocal each.
 #define ES_CHEB_K0 { \
     1.2201515410329777, -0.0314481013119645, 0.0015698838857300533, -0.00012849549581627802, \
@@ -183,7 +192,8 @@ ES_HD void ie_pair(int n, double x, double& in_, double& inp1) {
 // scaled I_n, I_{n+1} when the scaled K_n, K_{n+1} at the same argument are already known (they always are in the
 // exterior solution): the ratio f = I_{n+1}/I_n comes from Miller's backward recurrence
 // I_{k-1} = (2k/x) I_k + I_{k+1} started at M = n + 10 + sqrt(40 x) (I is the minimal solution, so the arbitrary
-// start is forgotten; M is 6+ orders beyond what 3e-16 needs on x in [0.5, 700], tests/test_hostmath.py) -- one fma
+// start is forgotten; M is 6+ orders beyond what rounding level needs on x in [0.5, 700]; the result carries the error
+// of K_n, K_{n+1}: 15 u = 3.3e-15 for n <= 11, tests/test_hostmath.py::test_truth) -- one fma
 // per order, no division -- and the normalisation from the Wronskian  I_n K_{n+1} + I_{n+1} K_n = 1/x  (unchanged
 // by the e^{-x}, e^{x} scalings).  ~40 orders at x = 18 instead of 45 series terms with two divisions each.
 ES_HD void ie_pair_from_k(int n, double x, double kn, double knp1, double& in_, double& inp1) {

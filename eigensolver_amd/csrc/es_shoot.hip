@@ -2247,13 +2247,14 @@ __global__ __launch_bounds__(256) void pack_records_kernel(es_root_table tab, in
   if (i > cap) return;
   const int count = d_count ? *d_count : count_host;
   double* o = out + (size_t)i * 6;
+  int n = count < cap ? count : cap;                     // records written: the receiver compares the count with it
+  if (n > tab.capacity) n = tab.capacity;
+  if (n < 0) n = 0;
   if (i == 0) {
-    o[0] = (double)count; o[1] = o[2] = o[3] = o[4] = o[5] = 0.0;
+    o[0] = (double)count; o[1] = (double)n; o[2] = o[3] = o[4] = o[5] = 0.0;
     return;
   }
   const int r = i - 1;
-  int n = count < cap ? count : cap;
-  if (n > tab.capacity) n = tab.capacity;
   if (r < n) {
     const int row = tab.d_row[r];
     o[0] = tab.d_k[r]; o[1] = tab.d_w[r]; o[2] = m; o[3] = tab.d_resid[r]; o[4] = (double)tab.d_flag[r];

@@ -64,8 +64,23 @@ def gather_root_tables(roots, m, world=None, group=None):
 # Record layout of the k-tiled grid search: (k, omega, m, resid, flag, global row).  Every rank sends a buffer of
 # cap + 1 rows whose row 0 carries its bracket count, so counts and records travel in the same all-gather and nothing
 # has to be read back on the host before the collective is enqueued (the two-phase exchange above needs the counts on
-# the host first).  Ranks whose count exceeds `cap` are detected when the gathered buffer is merged.
+# the host first).  Header row: field 0 = the rank's true bracket count, field 1 = the number of valid records that
+# follow = min(count, cap, capacity of the root table), the rest of the buffer is zero.  Ranks whose count exceeds
+# `cap`, or whose root table was too short for the count, are detected when the gathered buffer is merged.
 N_FIELDS = 6
+
+
+def _slot_count(header, cap, what):
+    """Record count of one slot from its header row; OverflowError when the slot does not hold all of them: the count
+    exceeds the exchange capacity, or the sender's root table (the valid records, field 1) was shorter than its count
+    and the slot is zero-filled beyond them."""
+    n, valid = int(round(header[0])), int(round(header[1]))
+    if n > cap:
+        raise OverflowError(f"root table of a {what} has {n} records, exchange capacity {cap}")
+    if n > valid:
+        raise OverflowError(f"root table of a {what} has {n} records, root table capacity {valid}: "
+                            f"only {valid} were written")
+    return n
 
 
 def pack_fixed(roots, count, m, rows_global, cap, ctx=None):
@@ -74,7 +89,10 @@ def pack_fixed(roots, count, m, rows_global, cap, ctx=None):
     nothing is read back.  With a library context (GPU tensors) the buffer is filled by ONE kernel
     (es_root_table_pack[_async]) on the CONTEXT's stream: the buffers it touches are allocated under that stream, so
     the caching allocator cannot hand them out again while the kernel is pending, whatever torch's current stream is.
-    The torch path is the same layout for CPU tensors (gloo tests)."""
+    The torch path is the same layout for CPU tensors (gloo tests).
+    Row 0 is the header (true count, valid records = min(count, cap, table length), 0, 0, 0, 0); rows 1 .. valid are
+    the records, the rest is zero.  A table shorter than its count (find_roots_async into a full table) is not an error
+    here -- nothing is read back -- but merge_fixed / merge_units raise OverflowError for it."""
     import torch
     dev = roots["w"].device
     if ctx is not None and roots["w"].is_cuda:
@@ -102,8 +120,9 @@ def pack_fixed(roots, count, m, rows_global, cap, ctx=None):
         return send
     send = torch.zeros((cap + 1, N_FIELDS), dtype=torch.float64, device=dev)
     count = int(count)
-    n = min(count, cap, roots["w"].numel())
+    n = max(min(count, cap, roots["w"].numel()), 0)
     send[0, 0] = float(count)
+    send[0, 1] = float(n)
     if n > 0:
         send[1:n + 1, 0] = roots["k"][:n]
         send[1:n + 1, 1] = roots["w"][:n]
@@ -155,9 +174,7 @@ def merge_fixed(buf):
     order (units outer, rows next, omega inner).  Host side."""
     b = buf.detach().cpu().numpy()
     cap = b.shape[1] - 1
-    counts = [int(round(b[r, 0, 0])) for r in range(b.shape[0])]
-    if max(counts) > cap:
-        raise OverflowError(f"root table of a rank has {max(counts)} records, exchange capacity {cap}")
+    counts = [_slot_count(b[r, 0], cap, "rank") for r in range(b.shape[0])]
     rec = np.concatenate([b[r, 1:1 + c] for r, c in enumerate(counts)], axis=0) if sum(counts) else np.zeros((0, N_FIELDS))
     order = np.lexsort((rec[:, 5], rec[:, 2]))            # stable: primary key unit, secondary key global row
     return rec[order], counts
@@ -180,9 +197,7 @@ def merge_units(buf, caps):
     for r in range(b.shape[0]):
         off, row_counts = 0, []
         for c in caps:
-            n = int(round(b[r, off, 0]))
-            if n > c:
-                raise OverflowError(f"root table of a unit has {n} records, exchange capacity {c}")
+            n = _slot_count(b[r, off], c, "unit")
             parts.append(b[r, off + 1:off + 1 + n])
             row_counts.append(n)
             off += c + 1

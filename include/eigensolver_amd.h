@@ -320,8 +320,11 @@ int es_context_get_refine_rule(const es_context* ctx, int* h_rule);
 int es_context_refine_stats(es_context* ctx, int64_t h[4]);
 
 /* Send buffer of the multi-GPU exchange (one all-gather of fixed-capacity buffers per step):
- * d_out is (cap + 1) x 6 doubles, row 0 = (count, 0, ...), rows 1 .. min(count, cap) = (k, omega, m, resid, flag,
- * global row) of the first records of `table`, the rest zero.  d_rows_global[local row] maps the rows of a k-tile to
+ * d_out is (cap + 1) x 6 doubles, row 0 = (count, valid, 0, ...) with valid = min(count, cap, table->capacity) the number
+ * of records that follow, rows 1 .. valid = (k, omega, m, resid, flag, global row) of the first records of `table`, the
+ * rest zero.  count > valid: the buffer does not hold every record (the receiver's merge raises).  es_root_table_pack
+ * rejects a table shorter than min(count, cap); the _async form, which cannot read the count, reports it through
+ * `valid`.  d_rows_global[local row] maps the rows of a k-tile to
  * the rows of the whole grid (NULL: identity).  Replaces the reference's positional pairing of two Queues
  * (Density_cylinder.py:1155-1168).  Asynchronous on the context's stream. */
 int es_root_table_pack(es_context* ctx, const es_root_table* table, int count, double m,

@@ -4,6 +4,7 @@ import os
 import socket
 
 import numpy as np
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -173,6 +174,96 @@ def test_k_tiled_grid_root_set_equals_single_rank():
 def test_fixed_exchange_reports_overflow():
     got = _run_tiled(2, 4)                 # capacity far below the number of brackets of a tile
     assert all(isinstance(got[r][0], str) and "capacity" in got[r][0] for r in range(2))
+
+
+def _worker_short_table(rank, world, port_no, q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port_no)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    port, k, W = _grid_problem()
+    rows = D.tile_rows(len(k), rank, world, strided=True)
+    roots, cnt = _tile_step(port, k, W, rows)
+    if rank == 1:                          # a root table that was too short for the search: 3 records fewer than its count
+        roots = {n: v[:cnt - 3] for n, v in roots.items()}
+    send = D.pack_fixed(roots, cnt, 1, torch.as_tensor(rows), 256)
+    header = send[0].tolist()
+    buf = D.gather_fixed(send, world)
+    try:
+        rec, counts = D.merge_fixed(buf)
+        q.put((rank, rec, (counts, cnt, header)))
+    except OverflowError as e:
+        q.put((rank, str(e), (None, cnt, header)))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_fixed_exchange_reports_a_short_root_table():
+    """A rank whose root table is shorter than its bracket count (find_roots_async into a full table) sends the true
+    count, the number of records it could write and a zero-filled remainder; with an ample exchange capacity (256) the
+    merge on EVERY rank raises and names the table capacity -- the zero rows (k = 0, omega = 0, row 0) are not merged."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port_no = _free_port()
+    procs = [ctx.Process(target=_worker_short_table, args=(r, 2, port_no, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = {}
+    for _ in range(2):
+        r, rec, extra = q.get(timeout=300)
+        got[r] = (rec, extra)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    cnt1 = got[1][1][1]
+    assert cnt1 > 8 and cnt1 < 256
+    assert got[0][1][2] == [float(got[0][1][1])] * 2 + [0.0] * 4           # rank 0: count = valid
+    assert got[1][1][2] == [float(cnt1), float(cnt1 - 3)] + [0.0] * 4      # rank 1: three records short
+    for r in range(2):
+        msg = got[r][0]
+        assert isinstance(msg, str), (r, got[r][1])
+        assert "root table capacity" in msg and "exchange capacity" not in msg and str(cnt1) in msg, msg
+
+
+def _hand_buffer(count, valid, cap, unit=1.0):
+    """(cap + 1, 6) send buffer with the given header and `valid` records (k = 1 + i, omega = 10 + i, global row i)."""
+    b = np.zeros((cap + 1, D.N_FIELDS))
+    b[0, 0], b[0, 1] = count, valid
+    for i in range(valid):
+        b[1 + i] = (1.0 + i, 10.0 + i, unit, 1e-3, 1.0, float(i))
+    return b
+
+
+def test_merge_checks_count_against_valid_records_and_capacity():
+    """merge_fixed / merge_units on hand-built buffers: count <= valid takes `count` records; count > valid (a short root
+    table) and count > cap (a short exchange buffer) raise OverflowError with their own messages."""
+    cap = 8
+    ok = torch.as_tensor(np.stack([_hand_buffer(3, 3, cap), _hand_buffer(0, 0, cap), _hand_buffer(8, 8, cap)]))
+    rec, counts = D.merge_fixed(ok)
+    assert counts == [3, 0, 8] and rec.shape == (11, D.N_FIELDS)
+    assert np.all(rec[:, 0] >= 1.0) and np.all(rec[:, 1] >= 10.0)          # no zero-filled row among the records
+    assert sorted(rec[:, 5].tolist()) == sorted(list(range(3)) + list(range(8)))
+    short = torch.as_tensor(np.stack([_hand_buffer(3, 3, cap), _hand_buffer(6, 4, cap)]))
+    with pytest.raises(OverflowError, match="6 records, root table capacity 4"):
+        D.merge_fixed(short)
+    over = torch.as_tensor(np.stack([_hand_buffer(3, 3, cap), _hand_buffer(9, 8, cap)]))
+    with pytest.raises(OverflowError, match="9 records, exchange capacity 8"):
+        D.merge_fixed(over)
+    both = torch.as_tensor(np.stack([_hand_buffer(20, 4, cap)]))            # both too short: the exchange capacity is named
+    with pytest.raises(OverflowError, match="20 records, exchange capacity 8"):
+        D.merge_fixed(both)
+    # the same through slots of several units: capacities 4 and 8 back to back
+    caps = [4, 8]
+    def units(h0, h1):
+        return torch.as_tensor(np.concatenate([_hand_buffer(*h0, caps[0], unit=1.0), _hand_buffer(*h1, caps[1], unit=2.0)])[None])
+    rec, per = D.merge_units(units((2, 2), (5, 5)), caps)
+    assert per == [[2, 5]] and rec.shape == (7, D.N_FIELDS) and rec[:, 2].tolist() == [1.0] * 2 + [2.0] * 5
+    assert np.all(rec[:, 0] >= 1.0)
+    with pytest.raises(OverflowError, match="5 records, root table capacity 3"):
+        D.merge_units(units((2, 2), (5, 3)), caps)
+    with pytest.raises(OverflowError, match="3 records, root table capacity 1"):
+        D.merge_units(units((3, 1), (5, 5)), caps)
+    with pytest.raises(OverflowError, match="5 records, exchange capacity 4"):
+        D.merge_units(units((5, 4), (5, 5)), caps)
 
 
 # ---- several units (azimuthal orders / modes) per rank: BASELINE configs[1], [2], [4] in bench.py --------------------

@@ -27,6 +27,41 @@ def test_pack_kernel_equals_torch_path(es_ctx, cap):
     else:
         with pytest.raises(OverflowError):
             D.merge_fixed(D.gather_fixed(torch.as_tensor(a), 1))
+    assert a[0].tolist() == [float(cnt), float(min(cnt, cap))] + [0.0] * 4     # header: true count, records written
+    gp.close()
+
+
+def test_short_root_table_is_reported_by_the_merge(es_ctx):
+    """A root table with fewer entries than the bracket count, packed into an ample exchange buffer (the state
+    find_roots_async leaves behind when its table was too small): kernel (count on the device: es_root_table_pack_async)
+    and torch path write the same buffer -- true count, records written, zero fill -- and the merge of either raises
+    instead of merging the zero rows as roots (k = 0, omega = 0, row 0)."""
+    import torch
+    from eigensolver_amd import ShootProblem, equilibrium as q
+    from eigensolver_amd import distributed as D
+    gp = ShootProblem(q.CylinderFlow(U_i0=0.6, width=1.0), "kink", ctx=es_ctx)
+    k = np.linspace(0.4, 3.9, 12)
+    W = 2.7 + (np.arange(160) + 0.5) * (4.95 - 2.7) / 160
+    Dg, st = gp.eval_grid(k, W)
+    roots, cnt = gp.find_roots(k, W, Dg, st, n_bisect=16)
+    cap = 64
+    assert 8 < cnt <= cap
+    rows = torch.arange(3, 3 + 7 * len(k), 7, device="cuda")
+    d_cnt = torch.tensor([cnt], dtype=torch.int32, device="cuda")
+    for keep in (cnt - 1, 4):
+        short = {key: v[:keep].contiguous() for key, v in roots.items()}
+        a = D.pack_fixed(short, d_cnt, 1, rows, cap, ctx=es_ctx)
+        b = D.pack_fixed(short, cnt, 1, rows, cap)                        # torch path
+        torch.cuda.synchronize()
+        bufs = [a.cpu().numpy(), b.cpu().numpy()]
+        assert np.array_equal(bufs[0], bufs[1])
+        for buf in bufs:
+            assert buf[0].tolist() == [float(cnt), float(keep)] + [0.0] * 4
+            assert np.array_equal(buf[1:1 + keep, 1], roots["w"][:keep].cpu().numpy()) and np.all(buf[1 + keep:] == 0)
+            with pytest.raises(OverflowError, match=f"{cnt} records, root table capacity {keep}"):
+                D.merge_fixed(D.gather_fixed(torch.as_tensor(buf), 1))
+            with pytest.raises(OverflowError, match=f"{cnt} records, root table capacity {keep}"):
+                D.merge_units(D.gather_fixed(torch.as_tensor(buf), 1), [cap])
     gp.close()
 
 

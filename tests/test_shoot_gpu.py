@@ -575,12 +575,20 @@ def test_find_roots_async_is_find_roots(es_ctx, name):
         a = Dm.pack_fixed({key: v for key, v in full.items()}, cnt, 2, rows, 64, ctx=es_ctx)
         torch.cuda.synchronize()
         assert int(a[0, 0].item()) == n                   # the header row carries the true count, overflow included
+        assert int(a[0, 1].item()) == min(n, cap, 64) and torch.all(a[0, 2:] == 0)   # and the number of records written
         if cap >= n:
             b = Dm.pack_fixed({key: v for key, v in full.items()}, n, 2, rows, 64, ctx=es_ctx)
             torch.cuda.synchronize()
             assert torch.equal(a, b)
+            rec, counts = Dm.merge_fixed(Dm.gather_fixed(a, 1))
+            assert counts == [n] and np.array_equal(np.sort(rec[:, 1]), np.sort(ref["w"][:n].cpu().numpy()))
         else:
             assert torch.all(a[1 + cap:] == 0) and torch.equal(a[1:1 + cap, 1], ref["w"][:cap])
+            # a table shorter than its count inside an ample exchange buffer (n <= 64): the zero-filled rows must not
+            # be merged as roots -- the merge raises and names the table capacity, not the exchange capacity
+            assert cap == 5 and n <= 64 and int(a[0, 1].item()) == 5
+            with pytest.raises(OverflowError, match=f"{n} records, root table capacity 5"):
+                Dm.merge_fixed(Dm.gather_fixed(a, 1))
     gp.close()
 
 
@@ -604,17 +612,63 @@ def test_grid_timer_counts_launches(es_ctx):
     gp.close()
 
 
-def test_more_tiles_than_one_grid_dimension_holds(es_ctx):
-    """One workgroup per tile: beyond 2^22 tiles the launch uses the y dimension of the grid (es_tile_grid).  4 196 304
-    rows of 64 frequencies (one tile each: 64 lanes x 1 point) of a 12-node cylinder; the rows cycle through 8
-    wavenumbers, so every row -- those past 2^22 in particular -- must carry the bits of the 8-row grid."""
-    import torch
+def _seam_problem(es_ctx, nw):
+    """The problem of the three y-dimension tests: a 12-node cylinder, 8 wavenumbers, nw phase speeds across the leaky
+    range, the continuum band and the body of the spectrum -- so a wrong row, a wrong status and an unwritten row all
+    show (nw = 16 on the CPU port: 104 OK, 8 leaky, 16 continuum points, 8 distinct rows of D)."""
     from eigensolver_amd import ShootProblem, equilibrium as q
     gp = ShootProblem(q.CylinderFlow(U_i0=0.6, width=1.0, n_nodes=12), "kink", None, ctx=es_ctx)
     k8 = np.linspace(0.4, 3.6, 8)
-    W = 2.7 + (np.arange(64) + 0.5) * (2.2 / 64)
+    W = 0.9 + (np.arange(nw) + 0.5) * (4.3 / nw)
+    return gp, k8, W
+
+
+def _seam_reference_guard(D8n, st8n):
+    """The 8-row reference can tell rows and statuses apart: >= 100 OK points, 8 distinct rows."""
+    assert ((st8n & 0x7f) == 0).sum() >= 100, ((st8n & 0x7f) == 0).sum()
+    assert len({D8n[i].tobytes() for i in range(8)}) == 8
+
+
+def _seam_windows_equal(D, st, D8n, st8n, windows):
+    nk = D.shape[0]
+    for lo, hi in windows:
+        assert 0 <= lo < hi <= nk, (lo, hi)
+        idx = np.arange(lo, hi) % 8
+        assert np.array_equal(D[lo:hi].cpu().numpy(), D8n[idx], equal_nan=True), lo
+        assert np.array_equal(st[lo:hi].cpu().numpy(), st8n[idx]), lo
+
+
+def _grid_shape(es_ctx, gp, nw):
+    import ctypes as C
+    from eigensolver_amd import _lib
+    pts, wpe, trk = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.check(es_ctx.handle, es_ctx.lib.es_shoot_grid_shape(es_ctx.handle, gp.handle, nw, C.byref(pts), C.byref(wpe), C.byref(trk)))
+    return pts.value
+
+
+def _shape_threads(nw, pts):
+    """shape_threads() of csrc/es_shoot.hip: lanes of a one-row workgroup for rows of nw frequencies, pts per lane."""
+    return min(max(((nw + pts - 1) // pts + 63) // 64 * 64, 64), 256)
+
+
+def test_more_tiles_than_one_grid_dimension_holds(es_ctx, monkeypatch):
+    """One workgroup per tile: beyond 2^22 tiles the launch uses the y dimension of the grid (es_tile_grid).  4 196 304
+    rows of 64 frequencies (one tile each: 64 lanes x 1 point) of a 12-node cylinder in the ONE-row kernel
+    (ES_GRID_ROWS2=0: two rows per workgroup would halve the workgroup count to below 2^22); the rows cycle through 8
+    wavenumbers, so every row -- those past 2^22 in particular -- must carry the bits of the 8-row grid.  The tile count is
+    no multiple of 2^22: the surplus workgroups of the last y row run the tile < ntiles guard."""
+    import torch
+    monkeypatch.setenv("ES_GRID_ROWS2", "0")
+    monkeypatch.delenv("ES_GRID_SHAPE", raising=False)
+    nw = 64
+    gp, k8, W = _seam_problem(es_ctx, nw)
     D8, st8 = gp.eval_grid(k8, W)
     nk = (1 << 22) + 2000
+    # the launch path this test exists for: a one-row shape whose tile count needs the y dimension
+    pts = _grid_shape(es_ctx, gp, nw)
+    assert pts > 0, pts
+    tiles = nk * -(-nw // (_shape_threads(nw, pts) * pts))
+    assert tiles > 2**22 and tiles % 2**22 != 0, tiles
     kk = torch.as_tensor(np.tile(k8, nk // 8 + 1)[:nk].copy(), device="cuda")
     D, st = gp.eval_grid(kk, W)
     assert D.shape == (nk, 64)
@@ -625,7 +679,60 @@ def test_more_tiles_than_one_grid_dimension_holds(es_ctx):
         assert np.array_equal(D[lo:hi].cpu().numpy(), D8n[idx], equal_nan=True), lo
         assert np.array_equal(st[lo:hi].cpu().numpy(), st8n[idx]), lo
     assert (st8n == 0).sum() > 100
-    del D, st
+    _seam_reference_guard(D8n, st8n)
+    del D, st, kk
+    gp.close()
+    torch.cuda.empty_cache()
+
+
+def test_two_rows_per_workgroup_past_one_grid_dimension(es_ctx, monkeypatch):
+    """shoot_grid_kernel_r2 beyond 2^22 workgroups: 2^23 + 4001 rows of 16 frequencies, two rows per workgroup =
+    4 196 305 workgroups (no multiple of 2^22; the row count is odd, so the second half of the last workgroup is empty).
+    Rows cycle through 8 wavenumbers: the first rows, the rows that straddle workgroup 2^22 (rows 2^23 - 16 ...) and the
+    tail with the final odd row carry the bits of the 8-row grid."""
+    import torch
+    monkeypatch.delenv("ES_GRID_ROWS2", raising=False)
+    monkeypatch.delenv("ES_GRID_SHAPE", raising=False)
+    nw = 16
+    gp, k8, W = _seam_problem(es_ctx, nw)
+    D8, st8 = gp.eval_grid(k8, W)
+    D8n, st8n = D8.cpu().numpy(), st8.cpu().numpy()
+    _seam_reference_guard(D8n, st8n)
+    nk = (1 << 23) + 4001
+    assert _grid_shape(es_ctx, gp, nw) < 0                   # the two-rows-per-workgroup kernel ...
+    groups = (nk + 1) // 2
+    assert groups > 2**22 and groups % 2**22 != 0 and nk % 2 == 1   # ... with a y dimension and an empty last half
+    kk = torch.as_tensor(np.tile(k8, nk // 8 + 1)[:nk].copy(), device="cuda")
+    D, st = gp.eval_grid(kk, W)
+    assert D.shape == (nk, nw) and st.shape == (nk, nw)
+    _seam_windows_equal(D, st, D8n, st8n, [(0, 2000), ((1 << 23) - 16, (1 << 23) + 2000), (nk - 2000, nk)])
+    del D, st, kk
+    gp.close()
+    torch.cuda.empty_cache()
+
+
+def test_screening_march_past_one_grid_dimension(es_ctx, monkeypatch):
+    """shoot_grid_f32_kernel (its own tile-index text) beyond 2^22 workgroups: 2^22 + 2000 rows of 16 frequencies, 64
+    lanes x 4 points = one tile per row, so the tile count is the row count (no multiple of 2^22).  Screened D (NaN ==
+    NaN) and status bytes (the unsure bit included) of every compared row are those of the 8-row screening."""
+    import torch
+    monkeypatch.delenv("ES_F32_VARIANT", raising=False)
+    nw = 16
+    gp, k8, W = _seam_problem(es_ctx, nw)
+    D8, st8 = gp.screen_grid(k8, W)
+    D8n, st8n = D8.cpu().numpy(), st8.cpu().numpy()
+    _seam_reference_guard(D8n, st8n)
+    nk = (1 << 22) + 2000
+    T, pts = 64, 4                                           # launch_grid_f32: T = 64 lanes for nw <= 256, 4 points per lane
+    assert _shape_threads(nw, pts) == T
+    tiles = nk * -(-nw // (T * pts))
+    assert tiles == nk and tiles > 2**22 and tiles % 2**22 != 0
+    kk = torch.as_tensor(np.tile(k8, nk // 8 + 1)[:nk].copy(), device="cuda")
+    D, st = gp.screen_grid(kk, W)
+    assert D.shape == (nk, nw) and st.shape == (nk, nw)
+    _seam_windows_equal(D, st, D8n, st8n, [(0, 2000), ((1 << 22) - 8, (1 << 22) + 2000 - 8), (nk - 2000, nk)])
+    del D, st, kk
+    gp.close()
     torch.cuda.empty_cache()
 
 
