@@ -217,6 +217,10 @@ def _sig(lib):
     lib.es_worker_run.argtypes = [vp, vp, C.POINTER(WorkerSpec), vp, i, vp, i, vp, vp, i, vp]
     # (4) closed-form uniform cylinder; (5) eigenfunctions
     lib.es_cyl_uniform_eval.argtypes = [vp, C.POINTER(CylUniformParams), vp, i, vp, i, i, vp, vp, vp]
+    lib.es_cyl_uniform_find_roots.argtypes = [vp, C.POINTER(CylUniformParams), i, i, vp, i, vp, i, i, i, d, vp, vp,
+                                              C.POINTER(RootTable), vp, C.POINTER(i)]
+    lib.es_cyl_uniform_find_roots_async.argtypes = [vp, C.POINTER(CylUniformParams), i, i, vp, i, vp, i, i, i, d, vp, vp,
+                                                    C.POINTER(RootTable), vp, vp]
     lib.es_shoot_eigenfunction.argtypes = [vp, vp, vp, vp, i, vp, vp, i, vp, vp, vp]
     # (6) complex frequencies
     lib.es_complex_eval_grid.argtypes = [vp, vp, i, vp, i, vp, i, vp, i, i, vp, vp, vp, vp]

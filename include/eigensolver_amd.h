@@ -385,6 +385,44 @@ int es_cyl_uniform_eval(es_context* ctx, const es_cyl_uniform_params* p, const d
                         const double* d_w, int nw, int w_mode,
                         double* d_D, double* d_rel /* may be NULL */, uint8_t* d_status);
 
+/* Root search of the closed form over (order, k, omega): the grid is evaluated and searched in ONE pass, without a D array
+ * unless the caller asks for it.
+ *   Orders: m = m_first + io, 0 <= io < n_orders, 0 <= m_first and m_first + n_orders - 1 <= 64.  The determinant of order m
+ *     is that of es_cyl_uniform_eval with p->m = p->m_ext = m (p->m and p->m_ext themselves are ignored); every other field
+ *     of p, axis_bc included, is used as given: sausage m = 0 and kink m >= 1 are two calls.
+ *   Brackets: D[j] D[j+1] < 0 between omega-neighbours of the same (order, row) with both ends ES_PT_OK, the rule of
+ *     es_shoot_find_roots; a bracket never spans a row or an order.  Each wave evaluates 63 cells plus the upper end of the
+ *     last one, so the neighbour of every cell comes from the next lane and no point is evaluated twice inside a wave.
+ *   Table: order outer, row next, omega inner.  d_row is the k-row index ik, d_order[pos] the order m (d_order has
+ *     `capacity` entries and may be NULL only if n_orders <= 1); the other columns mean what they do in es_shoot_find_roots.
+ *   Refinement: the ES_REFINE_SECTION rule described at es_shoot_find_roots -- R = ceil(n_bisect ln 2 / ln 17) rounds of
+ *     17-section (samples lo + (hi - lo)(j + 1)/17, the new bracket chosen by the first sample whose sign differs from
+ *     D(lo), NaN products compare false, a NaN D(lo) is never taken over), two regula-falsi steps, the last secant point is
+ *     the root and d_flag = (status == ES_PT_OK && rel < tol_percent) there.  The rule depends neither on the context's
+ *     refine rule (ES_REFINE_HYBRID has no meaning here) nor on the bracket count of the call: a grid tiled over calls,
+ *     orders or GPUs gives the one-call table, bit for bit.
+ *   d_D / d_status (optional, layout [(io * nk + ik) * nw + iw]): exactly what es_cyl_uniform_eval writes for that order.
+ *     When both are NULL the call writes nothing of size nk * nw except the bracket masks of the context (1/8 byte per
+ *     cell) -- the values at the ends of a bracket are recomputed by the same device function, the same bits.
+ *   Count and capacity as in es_shoot_find_roots: *h_count may exceed table->capacity, then ES_ERR_CAPACITY is returned and
+ *     the first `capacity` records are written and refined.  n_orders * nk * nw == 0: count 0, ES_SUCCESS.  Argument errors
+ *     as es_cyl_uniform_eval.
+ * The _async form synchronises nothing and reads nothing back: the count goes to the device word d_count, every launch
+ * is sized for the grid or for table->capacity and takes the count from device memory (size the table for the data, as for
+ * es_shoot_find_roots_async); ES_ERR_CAPACITY is never returned.  The one exception: a call that grows the bracket-scan
+ * scratch of the context (the first one at a larger grid) frees and allocates device memory, which synchronises. */
+int es_cyl_uniform_find_roots(es_context* ctx, const es_cyl_uniform_params* p, int m_first, int n_orders,
+                              const double* d_k, int nk, const double* d_w, int nw, int w_mode,
+                              int n_bisect, double tol_percent,
+                              double* d_D /* may be NULL */, uint8_t* d_status /* may be NULL */,
+                              es_root_table* table, int32_t* d_order /* capacity entries; may be NULL iff n_orders <= 1 */,
+                              int* h_count);
+int es_cyl_uniform_find_roots_async(es_context* ctx, const es_cyl_uniform_params* p, int m_first, int n_orders,
+                                    const double* d_k, int nk, const double* d_w, int nw, int w_mode,
+                                    int n_bisect, double tol_percent,
+                                    double* d_D /* may be NULL */, uint8_t* d_status /* may be NULL */,
+                                    es_root_table* table, int32_t* d_order, int32_t* d_count);
+
 /* ========================================================================================================
  * (5) Eigenfunctions at given (k, omega) -- the two-region solve the reference's analysis scripts repeat at a
  *     chosen root to plot P_T(r) and xi_r(r) (Cylinder/Non-uniform flow/Coronal/Eigenfunctions/
