@@ -227,4 +227,5 @@ def _sig(lib):
     lib.es_complex_eval_points.argtypes = [vp, vp, i, vp, vp, vp, i, vp, vp, vp, vp]
     lib.es_complex_find_roots.argtypes = [vp, vp, i, vp, i, vp, i, vp, i, i, vp, vp, vp, i, d,
                                           C.POINTER(ComplexRootTable), C.POINTER(i)]
+    lib.es_complex_eigenfunction.argtypes = [vp, vp, i, vp, vp, vp, i, vp, vp, i, vp, vp, vp, vp]
     return lib

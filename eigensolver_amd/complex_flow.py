@@ -136,6 +136,38 @@ class SlabComplexFlow:
                    "row": t["row"][:m], "flag": t["flag"][:m]}
             return out, n.value
 
+    def eigenfunction(self, mode, k, w, n_ext=500):
+        """Two-region solution at the complex (k, omega) pairs (es_complex_eigenfunction; replaces the solves of
+        complex_imag_flow_analysis.py:998-1043).  `w` is complex and `k` is broadcast against it, as in eval_points;
+        both may be tensors, e.g. roots["k"], roots["w"] of find_roots.  Dict of CUDA tensors: x_int [N],
+        value_int / flux_int [n, N] (complex128: Vx and P_T on the node grid, node 0 = boundary), x_ext [n, n_ext],
+        value_ext / flux_ext [n, n_ext] (complex128, far field to boundary), status [n] (uint8, that of eval_points;
+        rows that are not ES_PT_OK are NaN).  Scaled per unit V_e(-1): value_ext[:, -1] = 1 and
+        flux_ext[:, -1] - flux_int[:, 0] = D_c.  The reference's plot normalisation -- real and imaginary parts divided by
+        the maxima of the exterior real and imaginary parts, :1009-1043 -- is a host-side step on these arrays."""
+        import torch
+        p = self.problem(mode)
+        dev = f"cuda:{self.ctx.device}"
+        if isinstance(w, torch.Tensor):
+            w = w.to(device=dev, dtype=torch.complex128).reshape(-1)
+        else:
+            w = torch.as_tensor(np.asarray(w, dtype=complex).reshape(-1), device=dev)
+        dk = torch.broadcast_to(p._dev(k).reshape(-1), w.shape).contiguous()
+        dre, dim = w.real.contiguous(), w.imag.contiguous()
+        n, N, n_ext = w.numel(), int(p.desc.n_nodes), int(n_ext)
+        vi = torch.empty((n, N), dtype=torch.complex128, device=dev)
+        fi = torch.empty((n, N), dtype=torch.complex128, device=dev)
+        xe = torch.empty((n, n_ext), dtype=torch.float64, device=dev)
+        ve = torch.empty((n, n_ext), dtype=torch.complex128, device=dev)
+        fe = torch.empty((n, n_ext), dtype=torch.complex128, device=dev)
+        st = torch.empty(n, dtype=torch.uint8, device=dev)
+        rc = self.ctx.lib.es_complex_eigenfunction(self.ctx.handle, p.handle, self.variant, _lib.ptr(dk), _lib.ptr(dre),
+                                                   _lib.ptr(dim), n, _lib.ptr(vi), _lib.ptr(fi), n_ext, _lib.ptr(xe),
+                                                   _lib.ptr(ve), _lib.ptr(fe), _lib.ptr(st))
+        _lib.check(self.ctx.handle, rc)
+        x_int = torch.linspace(p.desc.x_boundary, p.desc.x_end, N, dtype=torch.float64, device=dev)
+        return dict(x_int=x_int, value_int=vi, flux_int=fi, x_ext=xe, value_ext=ve, flux_ext=fe, status=st)
+
     # ---- the reference's worker signature --------------------------------------------------------------------------
     def _worker(self, mode, wavenumber, ws, ks, ws_imag, ks_imag, freq):
         freq = np.asarray(freq, dtype=complex).reshape(-1)

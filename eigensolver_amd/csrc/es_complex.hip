@@ -1,4 +1,5 @@
-// K6: complex-frequency determinant of the flow slab, winding-number cell detection and complex secant refinement.
+// K6: complex-frequency determinant of the flow slab, winding-number cell detection and complex secant refinement,
+// eigenfunctions at given complex (k, omega).
 // See include/eigensolver_amd.h section (6) for the reference lines this replaces and oracle/slab_complex.py for the
 // CPU restatement (same algorithm: closed-form exterior, adjoint RK4 on the reference's ix grid with mid-point
 // coefficient sets, far-end condition by superposition).
@@ -80,36 +81,52 @@ __device__ __forceinline__ void cx_rhs(const CxCoef& A, cx p, cx q, cx& kp, cx& 
   kq = p + A.a22 * q;
 }
 
-__device__ __forceinline__ void cx_shoot_point(const ShootDev& P, int variant, double k, cx w, cx& D, double& rel,
-                                               uint8_t& st, double* __restrict__ sb) {
-  constexpr int NB = 3;
+__device__ __forceinline__ CxConsts cx_consts(const ShootDev& P, int variant, double k) {
   CxConsts C;
   C.k = k; C.k2 = k * k;
   C.kc2 = C.k2 * P.c2_i; C.kvA2 = C.k2 * P.vA2_i; C.kcT2 = C.k2 * P.cT2_i;
   C.k4c = C.k2 * C.k2 * P.cT2_i * P.c2_i;
   C.S_i = P.S_i; C.variant = variant;
-  // exterior (closed form, decaying branch), SF-X:369-371, :419-426
-  const cx Oe = w - mk(k * P.U_e);
-  const cx Oe2 = Oe * Oe;
-  const cx m_e = ((C.k2 * P.vAe2 - Oe2) * (C.k2 * P.ce2 - Oe2)) / (P.Se * (C.k2 * P.cTe2 - Oe2));
-  const cx p_e = (P.rho_e * P.Se) * ((C.k2 * P.cTe2 - Oe2) / (Oe * (C.k2 * P.ce2 - Oe2)));
-  int status = ES_PT_OK;
-  if (m_e.re < 0.0) status = ES_PT_LEAKY;                                             // `if m_e.real < 0: pass`
-  const cx mu = csqrt_(m_e);
-  const double R = P.R_factor / k;
-  const cx E2 = cexp_((-2.0 * (R - 1.0)) * mu);
-  const cx gq = mk(P.ic1) / mu;
-  const cx gp = P.ic0 + gq, gm = P.ic0 - gq;
-  const cx y = mu * ((gp - E2 * gm) / (gp + E2 * gm));
-  const cx outer = p_e * y;
-  if (status == ES_PT_OK && !cfinite(outer)) status = ES_PT_NONFINITE;
+  return C;
+}
 
-  // adjoint march of the functional Vx(+1) = (1, 0) . (u, v) from x = +1 back to x = -1
+// exterior (closed form, decaying branch), SF-X:369-371, :419-426:  Vx_e ~ gp e^{mu (x + R)} + gm e^{-mu (x + R)}
+struct CxExt {
+  cx Oe, p_e, mu, gp, gm, E2;      // E2 = e^{-2 mu (R - 1)}
+  cx outer;                        // p_e V_e'(-1) / V_e(-1)
+  double R;
+  int status;
+};
+
+__device__ __forceinline__ CxExt cx_exterior(const ShootDev& P, const CxConsts& C, double k, cx w) {
+  CxExt X;
+  X.Oe = w - mk(k * P.U_e);
+  const cx Oe2 = X.Oe * X.Oe;
+  const cx m_e = ((C.k2 * P.vAe2 - Oe2) * (C.k2 * P.ce2 - Oe2)) / (P.Se * (C.k2 * P.cTe2 - Oe2));
+  X.p_e = (P.rho_e * P.Se) * ((C.k2 * P.cTe2 - Oe2) / (X.Oe * (C.k2 * P.ce2 - Oe2)));
+  X.status = ES_PT_OK;
+  if (m_e.re < 0.0) X.status = ES_PT_LEAKY;                                           // `if m_e.real < 0: pass`
+  X.mu = csqrt_(m_e);
+  X.R = P.R_factor / k;
+  X.E2 = cexp_((-2.0 * (X.R - 1.0)) * X.mu);
+  const cx gq = mk(P.ic1) / X.mu;
+  X.gp = P.ic0 + gq; X.gm = P.ic0 - gq;
+  const cx y = X.mu * ((X.gp - X.E2 * X.gm) / (X.gp + X.E2 * X.gm));
+  X.outer = X.p_e * y;
+  if (X.status == ES_PT_OK && !cfinite(X.outer)) X.status = ES_PT_NONFINITE;
+  return X;
+}
+
+// adjoint march of the functional Vx(+1) = (1, 0) . (u, v) from x = +1 back to x = -1: Vx(+1) = zp u(-1) + zq v(-1).
+// Ub, dUb: the profile at the boundary node.  Every lane of the workgroup must call this (barriers of the staging).
+__device__ __forceinline__ void cx_adjoint(const ShootDev& P, const CxConsts& C, cx w, double* __restrict__ sb, cx& zp,
+                                           cx& zq, double& Ub, double& dUb) {
+  constexpr int NB = 3;
   const int nsteps = P.n_nodes - 1;
   const double h = P.h, h2 = 0.5 * P.h, h6 = P.h / 6.0, h3 = P.h / 3.0;
-  cx zp = mk(1.0), zq = mk(0.0);
+  zp = mk(1.0); zq = mk(0.0);
   CxCoef B0{mk(0.0), mk(0.0)};
-  double Ub = 0.0, dUb = 0.0;
+  Ub = 0.0; dUb = 0.0;
   const int nchunks = (nsteps + CH - 1) / CH;
   for (int c = nchunks - 1; c >= 0; --c) {
     const int c0 = c * CH;
@@ -136,20 +153,49 @@ __device__ __forceinline__ void cx_shoot_point(const ShootDev& P, int variant, d
       if (c == 0 && j == 0) { Ub = b1[SF_U]; dUb = b1[SF_DU]; }
     }
   }
-  // boundary: continuity of the displacement, symmetry condition by superposition, total pressures (SF-X:422, :455)
+}
+
+// total pressure of the interior state (u, v) = (Vx, Vx') at a node with Omega = Om: P_Ti (v - add u), SF-X:395, :401, :455
+__device__ __forceinline__ cx cx_total_pressure(const ShootDev& P, const CxConsts& C, cx Om, cx Om2, double dU, cx u, cx v) {
+  const cx PTi = (P.rho_i * P.S_i) * ((C.kcT2 - Om2) / (Om * (C.kc2 - Om2)));         // SF-X:395
+  const cx add = (C.variant == ES_CX_SFX) ? -(mk(C.k * dU) / Om) : mk(0.0);           // SF-X:401
+  return PTi * (v - add * u);
+}
+
+// boundary: continuity of the displacement, symmetry condition by superposition, total pressures (SF-X:422, :455)
+struct CxBoundary {
+  cx Vb, sv;          // interior state at x = -1 per unit V_e(-1): Vx, Vx'
+  cx D;               // outer - inner, NaN unless st == ES_PT_OK
+  double rel;
+  uint8_t st;
+};
+
+__device__ __forceinline__ CxBoundary cx_boundary(const ShootDev& P, const CxConsts& C, const CxExt& X, cx w, cx zp, cx zq,
+                                                  double Ub, double dUb) {
+  CxBoundary B;
   cx Omb, Omb2, m0b, Db;
   cx_terms(C, w, Ub, dUb, Omb, Omb2, m0b, Db);
-  const cx Vb = Omb / Oe;
-  const cx sv = ((P.slab_sign - zp) * Vb) / zq;
-  const cx PTi = (P.rho_i * P.S_i) * ((C.kcT2 - Omb2) / (Omb * (C.kc2 - Omb2)));      // SF-X:395
-  const cx add = (variant == ES_CX_SFX) ? -(mk(k * dUb) / Omb) : mk(0.0);             // SF-X:401
-  const cx inner = PTi * (sv - add * Vb);
-  const cx d = outer - inner;
-  st = (uint8_t)status;
-  D = d;
-  rel = cabs_(d) * 100.0 / fmax(cabs_(outer), cabs_(inner));
-  if (status != ES_PT_OK) { D = cx{NAN, NAN}; rel = NAN; return; }
-  if (!cfinite(d)) { st = ES_PT_NONFINITE; D = cx{NAN, NAN}; rel = NAN; }
+  B.Vb = Omb / X.Oe;
+  B.sv = ((P.slab_sign - zp) * B.Vb) / zq;
+  const cx inner = cx_total_pressure(P, C, Omb, Omb2, dUb, B.Vb, B.sv);
+  const cx d = X.outer - inner;
+  B.st = (uint8_t)X.status;
+  B.D = d;
+  B.rel = cabs_(d) * 100.0 / fmax(cabs_(X.outer), cabs_(inner));
+  if (X.status != ES_PT_OK) { B.D = cx{NAN, NAN}; B.rel = NAN; return B; }
+  if (!cfinite(d)) { B.st = ES_PT_NONFINITE; B.D = cx{NAN, NAN}; B.rel = NAN; }
+  return B;
+}
+
+__device__ __forceinline__ void cx_shoot_point(const ShootDev& P, int variant, double k, cx w, cx& D, double& rel,
+                                               uint8_t& st, double* __restrict__ sb) {
+  const CxConsts C = cx_consts(P, variant, k);
+  const CxExt X = cx_exterior(P, C, k, w);
+  cx zp, zq;
+  double Ub, dUb;
+  cx_adjoint(P, C, w, sb, zp, zq, Ub, dUb);
+  const CxBoundary B = cx_boundary(P, C, X, w, zp, zq, Ub, dUb);
+  D = B.D; rel = B.rel; st = B.st;
 }
 
 __device__ __forceinline__ cx cx_pick_w(int w_mode, double k, double wre, double wim) {
@@ -187,6 +233,114 @@ __global__ __launch_bounds__(256) void cx_eval_kernel(ShootDev P, int variant, c
     stout[i] = st;
     if (relout) relout[i] = rel;
   }
+}
+
+// ---- eigenfunctions at given (k, omega) -----------------------------------------------------------------------------
+// rhs of the forward system: A y with A = [[0, 1], [a21, a22]]
+__device__ __forceinline__ void cx_rhs_fwd(const CxCoef& A, cx u, cx v, cx& ku, cx& kv) {
+  ku = v;
+  kv = A.a21 * u + A.a22 * v;
+}
+
+// One (k, omega) pair per lane: the adjoint march of cx_shoot_point gives the boundary state (Vb, sv) that meets the
+// far-end condition, a forward RK4 march with the same coefficient sets writes (Vx, P_T) at every node.  val / flux are
+// interleaved (re, im) pairs, [i * N + node].  Lanes with i >= n march on dummy inputs (barriers) and store nothing.
+__global__ __launch_bounds__(64) void cx_eigen_interior_kernel(ShootDev P, int variant, const double* __restrict__ kv,
+                                                               const double* __restrict__ wre,
+                                                               const double* __restrict__ wim, int n,
+                                                               double* __restrict__ val, double* __restrict__ flux,
+                                                               uint8_t* __restrict__ stout) {
+  constexpr int NB = 3;
+  __shared__ double sb[3 * (2 * CH + 1)];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = i < n;
+  const double k = in ? kv[i] : 1.0;
+  const cx w = in ? cx{wre[i], wim[i]} : cx{1.0, 0.1};
+  const CxConsts C = cx_consts(P, variant, k);
+  const CxExt X = cx_exterior(P, C, k, w);
+  // (1) the row of the transfer matrix picked by the far-end condition -> boundary state, D_c and status
+  cx zp, zq;
+  double Ub, dUb;
+  cx_adjoint(P, C, w, sb, zp, zq, Ub, dUb);
+  const CxBoundary B = cx_boundary(P, C, X, w, zp, zq, Ub, dUb);
+  const bool ok = B.st == ES_PT_OK;
+  if (in) stout[i] = B.st;
+  // (2) forward march from the boundary, writing every node
+  cx u = B.Vb, v = B.sv;
+  auto store = [&](int node, double U, double dU) {
+    if (!in) return;
+    const cx Om = w - mk(k * U);
+    const cx pt = cx_total_pressure(P, C, Om, Om * Om, dU, u, v);
+    const size_t o = 2 * ((size_t)i * P.n_nodes + node);
+    val[o] = ok ? u.re : NAN;
+    val[o + 1] = ok ? u.im : NAN;
+    flux[o] = ok ? pt.re : NAN;
+    flux[o + 1] = ok ? pt.im : NAN;
+  };
+  const int nsteps = P.n_nodes - 1;
+  const double h = P.h, h2 = 0.5 * P.h, h6 = P.h / 6.0, h3 = P.h / 3.0;
+  CxCoef A0{mk(0.0), mk(0.0)};
+  const int nchunks = (nsteps + CH - 1) / CH;
+  for (int c = 0; c < nchunks; ++c) {
+    const int c0 = c * CH;
+    const int nst = (nsteps - c0 < CH) ? (nsteps - c0) : CH;
+    __syncthreads();
+#pragma unroll
+    for (int f = 0; f < NB; ++f)
+      for (int t = threadIdx.x; t < 2 * nst + 1; t += blockDim.x) sb[t * NB + f] = P.base[(size_t)f * P.npts + 2 * c0 + t];
+    __syncthreads();
+    if (c == 0) {
+      A0 = cx_coef(C, w, sb[SF_U], sb[SF_DU], sb[SF_DDU]);
+      store(0, sb[SF_U], sb[SF_DU]);
+    }
+    for (int j = 0; j < nst; ++j) {
+      const double* bm = sb + (2 * j + 1) * NB;
+      const double* b1 = sb + (2 * j + 2) * NB;
+      const CxCoef Am = cx_coef(C, w, bm[SF_U], bm[SF_DU], bm[SF_DDU]);
+      const CxCoef A1 = cx_coef(C, w, b1[SF_U], b1[SF_DU], b1[SF_DDU]);
+      cx k1u, k1v, k2u, k2v, k3u, k3v, k4u, k4v;
+      cx_rhs_fwd(A0, u, v, k1u, k1v);
+      cx_rhs_fwd(Am, u + h2 * k1u, v + h2 * k1v, k2u, k2v);
+      cx_rhs_fwd(Am, u + h2 * k2u, v + h2 * k2v, k3u, k3v);
+      cx_rhs_fwd(A1, u + h * k3u, v + h * k3v, k4u, k4v);
+      u = u + h6 * (k1u + k4u) + h3 * (k2u + k3u);
+      v = v + h6 * (k1v + k4v) + h3 * (k2v + k3v);
+      A0 = A1;
+      store(c0 + j + 1, b1[SF_U], b1[SF_DU]);
+    }
+  }
+}
+
+// One (pair, exterior point) per lane: Vx_e and p_e Vx_e' in closed form per unit V_e(-1), so that the last point of a
+// row is 1 + 0i and cx_exterior's `outer`.  st: the status the interior kernel wrote for the pair.
+__global__ __launch_bounds__(256) void cx_eigen_exterior_kernel(ShootDev P, int variant, const double* __restrict__ kv,
+                                                                const double* __restrict__ wre,
+                                                                const double* __restrict__ wim, int n, int n_ext,
+                                                                const uint8_t* __restrict__ st, double* __restrict__ xs,
+                                                                double* __restrict__ val, double* __restrict__ flux) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long)n * n_ext) return;
+  const int i = (int)(t / n_ext), j = (int)(t - (long)i * n_ext);
+  const double k = kv[i];
+  const cx w = cx{wre[i], wim[i]};
+  const CxExt X = cx_exterior(P, cx_consts(P, variant, k), k, w);
+  // np.linspace(-R, -1, n_ext)[j]
+  const double step = (-1.0 + X.R) / (double)(n_ext - 1);
+  const double x = (j == n_ext - 1) ? -1.0 : -X.R + (double)j * step;
+  const double ax = fabs(x);
+  cx v = cx{NAN, NAN}, f = cx{NAN, NAN};
+  if (st[i] == ES_PT_OK) {
+    const cx E2x = cexp_((-2.0 * (X.R - ax)) * X.mu);
+    const cx dec = cexp_((-(ax - 1.0)) * X.mu);
+    const cx den = X.gp + X.E2 * X.gm;
+    v = dec * ((X.gp + E2x * X.gm) / den);
+    f = X.p_e * (X.mu * (dec * ((X.gp - E2x * X.gm) / den)));                         // left_P = p_e_const * Vx'
+  }
+  xs[t] = x;
+  val[2 * t] = v.re;
+  val[2 * t + 1] = v.im;
+  flux[2 * t] = f.re;
+  flux[2 * t + 1] = f.im;
 }
 
 // ---- cells with a zero of D_c inside: winding number of D around the four corners ------------------------------
@@ -375,4 +529,34 @@ extern "C" int es_complex_find_roots(es_context* ctx, const es_problem* prob, in
     ES_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   }
   return (total > table->capacity) ? ES_ERR_CAPACITY : ES_SUCCESS;
+}
+
+extern "C" int es_complex_eigenfunction(es_context* ctx, const es_problem* prob, int variant, const double* d_k,
+                                        const double* d_w_re, const double* d_w_im, int n, double* d_int_value,
+                                        double* d_int_flux, int n_ext, double* d_ext_x, double* d_ext_value,
+                                        double* d_ext_flux, uint8_t* d_status) {
+  if (!ctx) return ES_ERR_INVALID_ARG;
+  int rc = check_cx(ctx, prob, variant);
+  if (rc) return rc;
+  ES_REQUIRE(ctx, n >= 0 && n_ext >= 0, "negative size");
+  ES_REQUIRE(ctx, n_ext == 0 || n_ext >= 2, "n_ext must be 0 or >= 2");
+  if (n == 0) return ES_SUCCESS;
+  ES_REQUIRE(ctx, d_k && d_w_re && d_w_im && d_int_value && d_int_flux, "null pointer");
+  ES_REQUIRE(ctx, n_ext == 0 || (d_ext_x && d_ext_value && d_ext_flux), "null exterior arrays");
+  ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (!d_status) {                                          // the exterior kernel reads the status of the interior march
+    rc = es_ensure_scratch(ctx, (size_t)n);
+    if (rc) return rc;
+    d_status = (uint8_t*)ctx->d_scratch;
+  }
+  hipLaunchKernelGGL(cx_eigen_interior_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, prob->dev, variant, d_k,
+                     d_w_re, d_w_im, n, d_int_value, d_int_flux, d_status);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  if (n_ext > 0) {
+    const long tot = (long)n * n_ext;
+    hipLaunchKernelGGL(cx_eigen_exterior_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream,
+                       prob->dev, variant, d_k, d_w_re, d_w_im, n, n_ext, d_status, d_ext_x, d_ext_value, d_ext_flux);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+  }
+  return ES_SUCCESS;
 }

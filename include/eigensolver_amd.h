@@ -485,6 +485,31 @@ int es_complex_find_roots(es_context* ctx, const es_problem* prob, int variant, 
                           const double* d_D_re, const double* d_D_im, const uint8_t* d_status, int n_iter,
                           double tol_percent, es_complex_root_table* table, int* out_count);
 
+/* Eigenfunctions at given complex (k, omega) -- what the reference's analysis script recomputes at a clicked root
+ * (Slab/Non uniform flow/COMPLEX ANALYSIS/complex_imag_flow_analysis.py:998-1013 exterior solve, :1023-1043 interior
+ * shoot, :1050-1072 plots of the real and imaginary parts of Vx and P_T over lx U ix), in the consistent reading of this
+ * section: everything complex.  Interior on the problem's node grid linspace(-1, +1, N): the adjoint march of D_c gives
+ * the boundary slope that meets the far-end condition Vx(+1) = -/+ Vx(-1), a forward RK4 march with the same node /
+ * mid-point coefficient sets writes value = Vx and flux = P_T = P_Ti (Vx' - add Vx) at every node (add = 0 for
+ * ES_CX_SFG).  Exterior on linspace(-L 2pi/k, -1, n_ext) in closed form, decaying branch: value = Vx_e, flux =
+ * p_e Vx_e'.  Both regions are per unit V_e(-1), the normalisation of D_c: the exterior value at the boundary is exactly
+ * 1 + 0i, the interior value at node 0 is Omega(-1) / Omega_e, and
+ *     exterior flux at the boundary - interior flux at node 0 = D_c
+ * of es_complex_eval_points (total pressure is continuous at a root).  The reference's plot normalisation (real and
+ * imaginary parts divided by the maxima of the exterior parts, :1009-1043) is a host-side step on these arrays.
+ * Complex arrays are interleaved (re, im) pairs of doubles (the layout of a C99 double complex); layout [i * N + j] /
+ * [i * n_ext + j] for pair i as in es_shoot_eigenfunction: interior node 0 is the boundary, exterior arrays run from
+ * the far field to the boundary.  n_ext is 0 (no exterior) or >= 2.  d_status[i] is the status es_complex_eval_points
+ * gives the pair; a pair that is not ES_PT_OK gets NaN in every value and flux entry (its d_ext_x is still written).
+ * Asynchronous on the context's stream (with d_status = NULL the first call at a larger n grows the context's scratch,
+ * which synchronises).  n == 0 returns ES_SUCCESS and touches nothing. */
+int es_complex_eigenfunction(es_context* ctx, const es_problem* prob, int variant,
+                             const double* d_k, const double* d_w_re, const double* d_w_im, int n,
+                             double* d_int_value, double* d_int_flux,      /* n x N complex      */
+                             int n_ext, double* d_ext_x,                   /* n x n_ext real     */
+                             double* d_ext_value, double* d_ext_flux,      /* n x n_ext complex  */
+                             uint8_t* d_status /* n, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
