@@ -433,6 +433,16 @@ int es_cyl_uniform_find_roots_async(es_context* ctx, const es_cyl_uniform_params
  *     of the reference's amplitude); the reference's plot normalisation (division by max|exterior|) is a host-side
  *     step on these arrays.  Layout: [i * N + j] / [i * n_ext + j] for pair i, node j (node 0 = boundary for the
  *     interior arrays; exterior arrays run from the far field to the boundary).
+ *     The pairs need not be roots: the two-region solution is defined at every (k, omega) whose exterior is bound;
+ *     flux_ext at the boundary minus flux_int at node 0 is the D of es_shoot_eval_points there (cylinders: up to the
+ *     truncation error of the grid -- their interior is integrated from the axis point outwards, the direction in which
+ *     the singular solution decays, so for any azimuthal order the arrays are good at the axis node too; the determinant
+ *     takes the boundary slope from its own adjoint march).
+ *     A pair whose exterior is ES_PT_LEAKY or ES_PT_NONFINITE gets NaN in all four of its value / flux rows; its d_ext_x
+ *     row is written as for any other pair, and the rows of the other pairs do not depend on it.  ES_PT_CONTINUUM is
+ *     not looked at here: the march steps over the singular point on the fixed grid as the determinant does.
+ *     n_ext = 0 skips the exterior (the three exterior pointers may then be NULL), n_ext = 1 is an error; n = 0 is a
+ *     successful call that touches nothing.
  * ====================================================================================================== */
 int es_shoot_eigenfunction(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w, int n,
                            double* d_int_value, double* d_int_flux,            /* n x N      */

@@ -320,6 +320,80 @@ def eigenfunction(prob, k, w, n_nodes, n_ext=500, rtol=1e-12):
     return dict(r_int=r_int, P_int=P_int, xi_int=X_int / r_int, r_ext=r_ext, P_ext=P_ext, xi_ext=xi_c * dP_ext)
 
 
+def exterior_terms(prob, k, w, n_ext):
+    """ORACLE: the closed-form exterior on linspace(-/+ L 2pi/k, -/+1, n_ext), scaled to |P_e(r_b)| = 1, with its
+    decaying part (b K_m) and its growing part (a I_m) kept apart:  P_e = P_K + P_I,  xi_e = xi_K + xi_I.
+    scipy's scaled Bessel functions at every gap, no asymptotic branch.  Returns dict(r_ext, P_K, P_I, xi_K, xi_I, gap)
+    with gap = mu (R - 1)."""
+    m_e, xi_c, _, _ = prob.exterior(k, w)
+    mu = math.sqrt(m_e)
+    sgn = prob.r_sign
+    R = prob.L_factor * 2.0 * math.pi / k
+    r_ext = np.linspace(sgn * R, sgn * 1.0, n_ext)
+    n = prob.m_ext
+    xR, xb = mu * R, mu
+    x = mu * np.abs(r_ext)
+    ic0, ic1 = prob.ic
+    g = ic1 / (sgn * mu)
+    KR, KR1 = special.kve(n, xR), special.kve(n + 1, xR)
+    IR, IR1 = special.ive(n, xR), special.ive(n + 1, xR)
+    dKR, dIR = -KR1 + (n / xR) * KR, IR1 + (n / xR) * IR
+    a_s, b_s = -(ic0 * dKR - g * KR), -(g * IR - ic0 * dIR)
+    Kx, Kx1, Ix, Ix1 = special.kve(n, x), special.kve(n + 1, x), special.ive(n, x), special.ive(n + 1, x)
+    dKx, dIx = -Kx1 + (n / x) * Kx, Ix1 + (n / x) * Ix
+    Kb, Ib = special.kve(n, xb), special.ive(n, xb)
+    den = abs(b_s * Kb + math.exp(-2 * (xR - xb)) * a_s * Ib)
+    dec = np.exp(-(x - xb))
+    E2x = np.exp(-2 * (xR - x))
+    P_K, P_I = dec * b_s * Kx / den, dec * E2x * a_s * Ix / den
+    dP_K, dP_I = sgn * mu * dec * b_s * dKx / den, sgn * mu * dec * E2x * a_s * dIx / den
+    return dict(r_ext=r_ext, P_K=P_K, P_I=P_I, xi_K=xi_c * dP_K, xi_I=xi_c * dP_I, gap=xR - xb)
+
+
+def eigenfunction_outward(prob, k, w, n_nodes, n_ext=500, rtol=1e-12):
+    """ORACLE: the two-region solution of `eigenfunction`, same outputs and normalisation, with the interior integrated
+    by DOP853 from the axis point r_ax OUT to the boundary r_b.  Towards the axis the singular solution grows like
+    r^-m in P and r^-(m+1) in xi_r (1e9 and 1e12 over the interval for m = 3), so an integration from the boundary
+    inwards amplifies its own error by that much; outwards the singular part decays and the error with it.
+      kink / rotation-kink: y = target y1 + beta y2 with y1, y2 started at (1, 0), (0, 1) at r_ax, target as in
+                            mismatch (P(r_ax) = target), beta from P(r_b) = P_b;
+      sausage:              y = beta (a12, -a11) at r_ax (P'(r_ax) = a11 P + a12 Xi = 0), beta from P(r_b) = P_b.
+    Additional keys: P_ext_K, P_ext_I, xi_ext_K, xi_ext_I (the two terms of the exterior closed form, exterior_terms)
+    and gap = mu (R - 1)."""
+    eq = prob.eq
+    m_e, xi_c, Pb, dPb = prob.exterior(k, w)
+    xi_e = xi_c * dPb
+    rb, ra = prob.r_sign, prob.r_sign * prob.r_axis
+    r_int = np.linspace(rb, ra, n_nodes)
+    out_nodes = r_int[::-1]
+
+    def march(y0):
+        sol = solve_ivp(prob._rhs, (ra, rb), np.asarray(y0, dtype=float), method="DOP853", rtol=rtol, atol=1e-300,
+                        t_eval=out_nodes, args=(k, w))
+        return sol.y[:, ::-1]                    # back to the order of r_int (boundary first)
+
+    if prob.axis_bc == "sausage":
+        D, C1, C2, C3, _, _ = prob.coefficients(np.array([ra]), k, w)
+        a11, a12 = -C1[0] / D[0], C3[0] / (ra * D[0])
+        nrm = math.hypot(a11, a12)
+        y = march([a12 / nrm, -a11 / nrm])
+        y = y * (Pb / y[0, 0])
+        P_int, X_int = y[0], y[1]
+    else:
+        if prob.axis_bc == "kink":
+            target = float(eq.B_phi(np.array([rb]))[0]) ** 2 * xi_e
+        else:
+            one = np.array([1.0])
+            target = -(float(eq.B_phi(one)[0]) ** 2 - float(eq.rho(one)[0]) * float(eq.v_phi(one)[0]) ** 2) * xi_e
+        y = march([1.0, 0.0, 0.0, 1.0])
+        beta = (Pb - target * y[0, 0]) / y[2, 0]
+        P_int, X_int = target * y[0] + beta * y[2], target * y[1] + beta * y[3]
+    e = exterior_terms(prob, k, w, n_ext)
+    return dict(r_int=r_int, P_int=P_int, xi_int=X_int / r_int, r_ext=e["r_ext"], P_ext=e["P_K"] + e["P_I"],
+                xi_ext=e["xi_K"] + e["xi_I"], P_ext_K=e["P_K"], P_ext_I=e["P_I"], xi_ext_K=e["xi_K"],
+                xi_ext_I=e["xi_I"], gap=e["gap"])
+
+
 def uniform_closed_form(eq, k, w, m, r_sign=-1.0, r_axis=1e-3, L_factor=3.0, ic=(1e-8, 1e-8), axis_bc="kink",
                         U_i=0.0):
     """ORACLE: the determinant of the UNIFORM cylinder (profile width -> infinity, the reference's benchmark case) in

@@ -268,3 +268,53 @@ class SlabProblem:
         if not np.isfinite(d):
             st = ST_NONFINITE
         return d, P_left, P_in, st
+
+
+def exterior_terms(prob, k, w, n_ext):
+    """ORACLE: the closed-form exterior of `SlabProblem.exterior` on linspace(-R, -1, n_ext), R = L 2 pi / k, scaled to
+    |Vx_e(-1)| = 1, with its two exponentials kept apart: Vx_e = V_dec + V_grow (decaying / growing away from the slab),
+    P_T = p_e Vx_e' = P_dec + P_grow.  Returns dict(x_ext, V_dec, V_grow, P_dec, P_grow, gap) with gap = mu (R - 1)."""
+    m_e, p_e, _, _ = prob.exterior(k, w)
+    mu = math.sqrt(m_e)
+    R = prob.L_factor * 2.0 * math.pi / k
+    x_ext = np.linspace(-R, -1.0, n_ext)
+    ax = np.abs(x_ext)
+    ic0, ic1 = prob.ic
+    gp, gm = ic0 + ic1 / mu, ic0 - ic1 / mu
+    den = abs(gp + math.exp(-2.0 * mu * (R - 1.0)) * gm)
+    dec = np.exp(-mu * (ax - 1.0))
+    V_dec, V_grow = dec * gp / den, dec * np.exp(-2.0 * mu * (R - ax)) * gm / den
+    return dict(x_ext=x_ext, V_dec=V_dec, V_grow=V_grow, P_dec=p_e * mu * V_dec, P_grow=-p_e * mu * V_grow,
+                gap=mu * (R - 1.0))
+
+
+def eigenfunction(prob, k, w, n_nodes, n_ext=500, rtol=1e-12):
+    """ORACLE: the two-region solution at (k, omega), normalised as `SlabProblem.mismatch` (|Vx_e(-1)| = 1).
+    Interior on linspace(-1, 1, n_nodes) by DOP853 from the boundary state (V_b, s) that mismatch forms (s = F Vx' for
+    the density slab, Vx' for the flow slabs): value Vx, flux P_T = s / omega (density) or (F / Omega) Vx' (flow).
+    Exterior from exterior_terms.  Returns dict(x_int, Vx_int, PT_int, x_ext, Vx_ext, PT_ext, Vx_ext_dec, Vx_ext_grow,
+    PT_ext_dec, PT_ext_grow, gap)."""
+    eq = prob.eq
+    m_e, p_e, Vb_e, dVb_e = prob.exterior(k, w)
+    xb = np.array([-1.0])
+    Om_b = prob._coef(xb, k, w)[5][0]
+    Oe = w - k * eq.U_e
+    Vb = Vb_e * Om_b / Oe if eq.kind != "density" else Vb_e
+    sol = solve_ivp(prob._rhs, (-1.0, 1.0), np.array([1.0, 0.0, 0.0, 1.0]), method="DOP853", rtol=rtol, atol=1e-300,
+                    args=(k, w))
+    T11, T12 = sol.y[0, -1], sol.y[2, -1]
+    sgn = -1.0 if prob.mode == "sausage" else 1.0
+    s = (sgn - T11) * Vb / T12
+    x_int = np.linspace(-1.0, 1.0, n_nodes)
+    sol = solve_ivp(prob._rhs, (-1.0, 1.0), np.array([Vb, s]), method="DOP853", rtol=rtol, atol=1e-300, t_eval=x_int,
+                    args=(k, w))
+    Vx, v = sol.y[0], sol.y[1]
+    if eq.kind == "density":
+        PT = v / w
+    else:
+        _, _, _, _, _, Om, _, F = prob._coef(x_int, k, w)
+        PT = (F / Om) * v
+    e = exterior_terms(prob, k, w, n_ext)
+    return dict(x_int=x_int, Vx_int=Vx, PT_int=PT, x_ext=e["x_ext"], Vx_ext=e["V_dec"] + e["V_grow"],
+                PT_ext=e["P_dec"] + e["P_grow"], Vx_ext_dec=e["V_dec"], Vx_ext_grow=e["V_grow"],
+                PT_ext_dec=e["P_dec"], PT_ext_grow=e["P_grow"], gap=e["gap"])

@@ -159,3 +159,53 @@ def test_round3_entry_points_reject_bad_arguments(es_ctx, monkeypatch):
     assert r1[1] == r2[1] and torch.equal(r1[0]["w"], r2[0]["w"])
     gs.close()
     gp.close()
+
+
+def test_eigenfunction_rejects_bad_arguments(es_ctx):
+    """es_shoot_eigenfunction: null context / problem / arrays, negative sizes, n_ext == 1; n_ext = 0 with null exterior
+    arrays and n = 0 are fine.  Nothing here launches with an invalid pointer: every rejected call returns before the launch
+    and the accepted ones get valid buffers."""
+    import torch
+    from eigensolver_amd import _lib, ShootProblem, equilibrium as q
+    lib = es_ctx.lib
+    gp = ShootProblem(q.CylinderFlow(U_i0=0.6, width=1.0, n_nodes=130), "kink", ctx=es_ctx)
+    N, n, n_ext = 130, 3, 4
+    k = torch.tensor([1.0, 1.5, 2.0], dtype=torch.float64, device="cuda")
+    w = 3.5 * k
+    vi, fi = (torch.full((n, N), 5.0, dtype=torch.float64, device="cuda") for _ in range(2))
+    xe, ve, fe = (torch.full((n, n_ext), 5.0, dtype=torch.float64, device="cuda") for _ in range(3))
+    good = [es_ctx.handle, gp.handle, _lib.ptr(k), _lib.ptr(w), n, _lib.ptr(vi), _lib.ptr(fi), n_ext, _lib.ptr(xe),
+            _lib.ptr(ve), _lib.ptr(fe)]
+
+    def call(**change):
+        a = list(good)
+        for pos, val in change.items():
+            a[int(pos[1:])] = val
+        return lib.es_shoot_eigenfunction(*a)
+
+    assert call(a0=None) == 1                                                       # no context: nowhere to leave a message
+    for change, text in (({"a1": None}, b"null problem"), ({"a4": -1}, b"negative size"), ({"a7": -1}, b"negative size"),
+                         ({"a7": 1}, b"n_ext must be 0 or >= 2"), ({"a2": None}, b"null pointer"),
+                         ({"a3": None}, b"null pointer"), ({"a5": None}, b"null pointer"), ({"a6": None}, b"null pointer"),
+                         ({"a8": None}, b"null exterior arrays"), ({"a9": None}, b"null exterior arrays"),
+                         ({"a10": None}, b"null exterior arrays")):
+        assert call(**change) == 1, change
+        assert text in lib.es_last_error(es_ctx.handle), (change, lib.es_last_error(es_ctx.handle))
+    es_ctx.synchronize()
+    for t in (vi, fi, xe, ve, fe):
+        assert bool((t == 5.0).all())                                               # a rejected call writes nothing
+    # n = 0: success, nothing touched, whatever the arrays
+    assert call(a4=0) == 0
+    assert call(a4=0, a2=None, a3=None, a5=None, a6=None, a8=None, a9=None, a10=None) == 0
+    es_ctx.synchronize()
+    for t in (vi, fi, xe, ve, fe):
+        assert bool((t == 5.0).all())
+    # n_ext = 0 with null exterior arrays: the interior alone
+    assert call(a7=0, a8=None, a9=None, a10=None) == 0
+    es_ctx.synchronize()
+    assert bool(torch.isfinite(vi).all()) and bool((vi != 5.0).any()) and bool((xe == 5.0).all())
+    # and the whole call
+    assert call() == 0
+    es_ctx.synchronize()
+    assert bool(torch.isfinite(ve).all()) and bool((xe[:, -1] == -1.0).all())
+    gp.close()
