@@ -18,6 +18,9 @@ struct es_context {
   int* d_block_counts = nullptr;   size_t blocks_cap = 0;     // per-256-cell block counts / exclusive offsets
   int* d_total = nullptr;                                     // device-side total count
   int* h_total = nullptr;                                     // pinned host mirror
+  // the four count words of es_shoot_find_roots_screened (the async searches use the caller's) and their pinned mirror
+  int32_t* d_screen = nullptr;
+  int32_t* h_screen = nullptr;
   // general call scratch (worker tables and frame stacks, refinement start data): grown on demand, never shrunk;
   // calls on one context are serialised by its stream, so one buffer suffices
   void* d_scratch = nullptr;       size_t scratch_cap = 0;
@@ -77,6 +80,12 @@ int es_ensure_scan_scratch(es_context* ctx, size_t cells);
 int es_scan_block_counts(es_context* ctx, int nblocks, int* h_total_out);
 // The scan alone, enqueued: offsets in ctx->d_block_counts, total in ctx->d_total, nothing read back.
 int es_scan_block_counts_async(es_context* ctx, int nblocks);
+
+// The count convention of every kernel that takes (d_n, n_max): the launch is sized for n_max; the count is *d_n, read from
+// device memory and capped at n_max, or n_max itself when d_n == nullptr (the host knows the count).
+__device__ __forceinline__ int es_count(const int* d_n, int n_max) {
+  return d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+}
 
 // Position of a flagged cell inside the ordered output, from the masks and the scanned block offsets.
 __device__ __forceinline__ int es_cell_rank(const uint64_t* __restrict__ masks, const int* __restrict__ block_off,

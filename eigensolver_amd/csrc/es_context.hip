@@ -42,9 +42,13 @@ extern "C" int es_context_create(int device, void* stream, es_context** out) {
   if (hipSetDevice(device) != hipSuccess) { delete ctx; return ES_ERR_HIP; }
   if (hipMalloc(&ctx->d_total, sizeof(int)) != hipSuccess) { delete ctx; return ES_ERR_HIP; }
   if (hipHostMalloc(&ctx->h_total, sizeof(int)) != hipSuccess) { (void)hipFree(ctx->d_total); delete ctx; return ES_ERR_HIP; }
-  if (hipMalloc(&ctx->d_refine_stats, 4 * sizeof(unsigned long long)) != hipSuccess ||
+  if (hipMalloc(&ctx->d_screen, 4 * sizeof(int32_t)) != hipSuccess ||
+      hipHostMalloc(&ctx->h_screen, 4 * sizeof(int32_t)) != hipSuccess ||
+      hipMalloc(&ctx->d_refine_stats, 4 * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(ctx->d_refine_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess) {
     if (ctx->d_refine_stats) (void)hipFree(ctx->d_refine_stats);
+    if (ctx->d_screen) (void)hipFree(ctx->d_screen);
+    if (ctx->h_screen) (void)hipHostFree(ctx->h_screen);
     (void)hipFree(ctx->d_total); (void)hipHostFree(ctx->h_total); delete ctx; return ES_ERR_HIP;
   }
   *out = ctx;
@@ -63,6 +67,8 @@ extern "C" int es_context_destroy(es_context* ctx) {
   if (ctx->d_refine_stats) (void)hipFree(ctx->d_refine_stats);
   if (ctx->d_total) (void)hipFree(ctx->d_total);
   if (ctx->h_total) (void)hipHostFree(ctx->h_total);
+  if (ctx->d_screen) (void)hipFree(ctx->d_screen);
+  if (ctx->h_screen) (void)hipHostFree(ctx->h_screen);
   for (auto& e : ctx->timer_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   delete ctx;
   return ES_SUCCESS;

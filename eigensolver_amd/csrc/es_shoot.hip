@@ -18,8 +18,9 @@
 //    the final classification with the reference's acceptance measure.  Both cylinder families launch one round / one step
 //    per launch (ONE); the bracket count may stay on the device (es_shoot_find_roots_async).
 //  * shoot_grid_f32_kernel: fp32 screening march of es_shoot_find_roots_mixed.
-//  * *_dcount_kernel: the re-evaluation / bracket-end steps of the mixed search with their counts in device memory
-//    (es_shoot_find_roots_screened_async): launches sized for the grid or the table capacity.
+//  * Every kernel that works on a list (points, brackets) takes (d_n, n_max) and starts with n = es_count(d_n, n_max)
+//    (es_common.hpp): the launch is sized for n_max, the count is n_max itself (d_n == nullptr: the host knows it) or is
+//    read from device memory (the asynchronous searches: n_max is the grid size or the table capacity).
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
@@ -161,12 +162,16 @@ __global__ __launch_bounds__(256) void fill_dead_columns_kernel(ShootDev P, cons
   }
 }
 
+// One workgroup per 256 points of the launch bound.  The early exit is workgroup-uniform and comes before shoot_point's
+// LDS staging, whose barriers every lane of a live workgroup reaches.
 template <int FAM>
 __global__ __launch_bounds__(256) void shoot_points_kernel(ShootDev P, const double* __restrict__ kv,
-                                                           const double* __restrict__ wv, int n,
-                                                           double* __restrict__ Dout, double* __restrict__ relout,
-                                                           uint8_t* __restrict__ stout) {
+                                                           const double* __restrict__ wv, const int* __restrict__ d_n,
+                                                           int n_max, double* __restrict__ Dout,
+                                                           double* __restrict__ relout, uint8_t* __restrict__ stout) {
   ES_POINT_LDS(FAM);
+  const int n = es_count(d_n, n_max);
+  if ((long)blockIdx.x * 256 >= (long)n) return;                                          // workgroup-uniform
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;
   const double k = in ? kv[i] : 1.0;
@@ -269,7 +274,7 @@ void refine_kernel(ShootDev P, es_root_table tab, double* d_lo, double* d_hi, co
                    int n_rounds, int n_polish, double tol_percent) {                      // d_lo / d_hi alias table columns
   // bracket count: from device memory (es_shoot_find_roots_async: the host never reads it; the launch is sized for
   // n_max = the table capacity and the workgroups beyond the count return at once) or n_max itself
-  const int n = d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+  const int n = es_count(d_n, n_max);
   if ((int)(blockIdx.x * REFINE_WAVES * (64 / LANES)) >= n) return;                       // workgroup-uniform
   constexpr int GROUPS = 64 / LANES;
   constexpr int WTBL = GROUPS * (2 * (CHR > 0 ? CHR : 1) + 1) * FamTraits<FAM>::NE;      // doubles per wave
@@ -354,7 +359,7 @@ __global__ __launch_bounds__(64 * REFINE_WAVES) __attribute__((amdgpu_waves_per_
 void refine_polish_kernel(ShootDev P, es_root_table tab, double* d_lo, double* d_hi, const int* __restrict__ d_n,
                           int n_max, int n_polish, double tol_percent) {   // d_lo / d_hi alias table columns (no restrict)
   ES_POINT_LDS(FAM);
-  const int n = d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+  const int n = es_count(d_n, n_max);
   if ((int)(blockIdx.x * (64 * REFINE_WAVES)) >= n) return;                               // workgroup-uniform
   const int i = blockIdx.x * (64 * REFINE_WAVES) + (int)threadIdx.x;
   const bool in = i < n;
@@ -419,7 +424,7 @@ void refine_superlinear_kernel(ShootDev P, es_root_table tab, const double* d_lo
                                const int* __restrict__ d_n, int n_max, int step, double tol_percent,
                                unsigned long long* stats) {
   ES_POINT_LDS(FAM);
-  const int n = d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+  const int n = es_count(d_n, n_max);
   if ((int)(blockIdx.x * (64 * REFINE_WAVES)) >= n) return;                               // workgroup-uniform
   const int i = blockIdx.x * (64 * REFINE_WAVES) + (int)threadIdx.x;
   const bool in = i < n;
@@ -483,7 +488,7 @@ __global__ __launch_bounds__(256) void hybrid_flag_kernel(const int* __restrict_
                                                           int n_max, uint64_t* __restrict__ masks,
                                                           int* __restrict__ block_counts, unsigned long long* stats) {
   __shared__ int wave_cnt[4];
-  const int n = d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+  const int n = es_count(d_n, n_max);
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   const bool flag = i < n && (info[i] >> 2) != HYB_KEPT;
   const uint64_t m = __ballot(flag);
@@ -504,7 +509,7 @@ __global__ __launch_bounds__(256) void hybrid_gather_kernel(es_root_table tab, e
                                                             const uint64_t* __restrict__ masks,
                                                             const int* __restrict__ block_off,
                                                             const int* __restrict__ d_n, int n_max) {
-  const int n = d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+  const int n = es_count(d_n, n_max);
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   if (i >= n) return;
   if (!((masks[i >> 6] >> (i & 63)) & 1ull)) return;
@@ -1052,18 +1057,21 @@ __global__ __launch_bounds__(256) void unsure_gather_kernel(const double* __rest
 }
 
 __global__ __launch_bounds__(256) void scatter_points_kernel(const long* __restrict__ pcell, const double* __restrict__ pD,
-                                                             const uint8_t* __restrict__ pst, int n,
-                                                             double* __restrict__ D, uint8_t* __restrict__ st) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
+                                                             const uint8_t* __restrict__ pst, const int* __restrict__ d_n,
+                                                             int n_max, double* __restrict__ D, uint8_t* __restrict__ st) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)es_count(d_n, n_max)) return;
   D[pcell[i]] = pD[i];
   st[pcell[i]] = pst[i];
 }
 
-// both ends of every bracket as (k, omega) pairs: [0, n) lower ends, [n, 2n) upper ends
-__global__ __launch_bounds__(256) void bracket_ends_kernel(es_root_table tab, int n, double* __restrict__ pk,
-                                                           double* __restrict__ pw) {
+// both ends of the first n brackets as (k, omega) pairs: [0, n) lower ends, [n, 2n) upper ends; the point count 2n goes
+// to *d_npts for the fp64 evaluation that follows (d_n and d_npts are words of one array: no __restrict__)
+__global__ __launch_bounds__(256) void bracket_end_points_kernel(es_root_table tab, const int* d_n, int n_max, int* d_npts,
+                                                                 double* __restrict__ pk, double* __restrict__ pw) {
+  const int n = es_count(d_n, n_max);
   const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) *d_npts = 2 * n;
   if (i >= n) return;
   pk[i] = tab.d_k[i]; pk[n + i] = tab.d_k[i];
   pw[i] = tab.d_w_lo[i]; pw[n + i] = tab.d_w_hi[i];
@@ -1071,9 +1079,10 @@ __global__ __launch_bounds__(256) void bracket_ends_kernel(es_root_table tab, in
 
 // fp64 values at the bracket ends replace the screening values the refinement starts from; a bracket whose fp64 ends do
 // not change sign (or are not both ES_PT_OK) would be a failure of the screening bound: counted, never hidden
-__global__ __launch_bounds__(256) void bracket_ends_store_kernel(const double* __restrict__ pD, const uint8_t* __restrict__ pst,
-                                                                 int n, double* __restrict__ d_lo, double* __restrict__ d_hi,
-                                                                 int* __restrict__ violations) {
+__global__ __launch_bounds__(256) void bracket_end_values_kernel(const double* __restrict__ pD, const uint8_t* __restrict__ pst,
+                                                                 const int* d_n, int n_max, double* __restrict__ d_lo,
+                                                                 double* __restrict__ d_hi, int* violations) {
+  const int n = es_count(d_n, n_max);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const double a = pD[i], b = pD[n + i];
@@ -1082,77 +1091,28 @@ __global__ __launch_bounds__(256) void bracket_ends_store_kernel(const double* _
   if (!(pst[i] == ES_PT_OK && pst[n + i] == ES_PT_OK && a * b < 0.0)) atomicAdd(violations, 1);
 }
 
-// ---- the same steps with the counts in device memory (es_shoot_find_roots_screened_async) ------------------------------
-// The host knows only the grid size and the table capacity: every launch below is sized for those, reads its count from
-// the caller's count words (d_counts[0] brackets, [1] unsure points, [2] bracket-end points) and its workgroups beyond the
-// count return at once.  The arithmetic is that of the kernels above, line for line.
-
-// shoot_points_kernel with n = *d_n; one workgroup per 256 points of the launch bound.  The early exit is workgroup-
-// uniform and comes before shoot_point's LDS staging, whose barriers every lane of a live workgroup reaches.
-template <int FAM>
-__global__ __launch_bounds__(256) void shoot_points_dcount_kernel(ShootDev P, const double* __restrict__ kv,
-                                                                  const double* __restrict__ wv, const int* __restrict__ d_n,
-                                                                  double* __restrict__ Dout, uint8_t* __restrict__ stout) {
-  ES_POINT_LDS(FAM);
-  const int n = *d_n;
-  if ((long)blockIdx.x * 256 >= (long)n) return;                                          // workgroup-uniform
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool in = i < n;
-  const double k = in ? kv[i] : 1.0;
-  const double w = in ? wv[i] : 1.0;
-  double D, rel; uint8_t st;
-  shoot_point<FAM>(P, k, w, w, D, rel, st, es_point_lds);
-  if (in) {
-    Dout[i] = D;
-    stout[i] = st;
-  }
-}
-
-__global__ __launch_bounds__(256) void scatter_points_dcount_kernel(const long* __restrict__ pcell,
-                                                                    const double* __restrict__ pD,
-                                                                    const uint8_t* __restrict__ pst,
-                                                                    const int* __restrict__ d_n, double* __restrict__ D,
-                                                                    uint8_t* __restrict__ st) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long)*d_n) return;
-  D[pcell[i]] = pD[i];
-  st[pcell[i]] = pst[i];
-}
-
-// bracket_ends_kernel for n = min(d_counts[0], capacity) brackets ([0, n) lower ends, [n, 2n) upper ends); the point
-// count 2n goes to d_counts[2] for the fp64 evaluation that follows
-__global__ __launch_bounds__(256) void bracket_end_points_dcount_kernel(es_root_table tab, int32_t* d_counts,
-                                                                  double* __restrict__ pk, double* __restrict__ pw) {
-  const int total = d_counts[0];
-  const int n = total < tab.capacity ? total : tab.capacity;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i == 0) d_counts[2] = 2 * n;
-  if (i >= n) return;
-  pk[i] = tab.d_k[i]; pk[n + i] = tab.d_k[i];
-  pw[i] = tab.d_w_lo[i]; pw[n + i] = tab.d_w_hi[i];
-}
-
-// the fp64 end values of the n = min(d_counts[0], cap) brackets go where the refinement reads them (the arithmetic of
-// the kernel above); violations are counted into d_counts[3]
-__global__ __launch_bounds__(256) void bracket_end_values_dcount_kernel(const double* __restrict__ pD,
-                                                                        const uint8_t* __restrict__ pst, int32_t* d_counts,
-                                                                        int cap, double* __restrict__ d_lo,
-                                                                        double* __restrict__ d_hi) {
-  const int total = d_counts[0];
-  const int n = total < cap ? total : cap;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const double a = pD[i], b = pD[n + i];
-  d_lo[i] = a;
-  d_hi[i] = b;
-  if (!(pst[i] == ES_PT_OK && pst[n + i] == ES_PT_OK && a * b < 0.0)) atomicAdd(d_counts + 3, 1);
-}
-
 // ---- host side -------------------------------------------------------------------------------------------------
 int check_problem(es_context* ctx, const es_problem* prob) {
   ES_REQUIRE(ctx, prob != nullptr, "null problem");
   return ES_SUCCESS;
 }
+
+int check_root_table(es_context* ctx, const es_root_table* table) {
+  ES_REQUIRE(ctx, table->capacity == 0 || (table->d_k && table->d_w && table->d_w_lo && table->d_w_hi &&
+                                           table->d_resid && table->d_row && table->d_flag),
+             "null root table arrays");
+  return ES_SUCCESS;
+}
+
+// `return CALL(FAM)` with the family of a problem as the template argument
+#define ES_DISPATCH_FAMILY(fam, CALL)                      \
+  switch (fam) {                                           \
+    case FAM_CYL0: return CALL(FAM_CYL0);                  \
+    case FAM_CYLT: return CALL(FAM_CYLT);                  \
+    case FAM_SLABD: return CALL(FAM_SLABD);                \
+    case FAM_SLABF: return CALL(FAM_SLABF);                \
+    default: return ES_ERR_UNSUPPORTED;                    \
+  }
 
 // Launch shape of the grid kernel = (PTS points per lane, WPE waves per SIMD the register cap allows).  Every shape runs
 // workgroups of at most 256 threads (one wave per SIMD of a CU) over tiles (k-row, omega-segment of T * PTS points) and
@@ -1341,13 +1301,25 @@ int launch_grid(es_context* ctx, const es_problem* prob, const double* d_k, int 
   return ES_SUCCESS;
 }
 
+// a launch bound as the kernels take it: counts are int32, a launch may be sized for more (a grid beyond 2^31 cells)
+inline int es_bound(long n_max) { return (int)(n_max < INT32_MAX ? n_max : INT32_MAX); }
+inline dim3 es_blocks(long n_max) { return dim3((unsigned)((n_max + 255) / 256)); }
+
+// fp64 evaluation of es_count(d_n, n_max) points, the launch sized for n_max (d_rel is optional)
 template <int FAM>
-int launch_points(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w, int n,
+int launch_points(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w, const int* d_n, long n_max,
                   double* d_D, double* d_rel, uint8_t* d_status) {
-  hipLaunchKernelGGL((shoot_points_kernel<FAM>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, prob->dev, d_k,
-                     d_w, n, d_D, d_rel, d_status);
+  hipLaunchKernelGGL((shoot_points_kernel<FAM>), es_blocks(n_max), dim3(256), 0, ctx->stream, prob->dev, d_k, d_w, d_n,
+                     es_bound(n_max), d_D, d_rel, d_status);
   ES_HIP_CHECK(ctx, hipGetLastError());
   return ES_SUCCESS;
+}
+
+int dispatch_points(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w, const int* d_n, long n_max,
+                    double* d_D, double* d_rel, uint8_t* d_status) {
+#define CALL_PTS(F) launch_points<F>(ctx, prob, d_k, d_w, d_n, n_max, d_D, d_rel, d_status)
+  ES_DISPATCH_FAMILY(prob->dev.family, CALL_PTS)
+#undef CALL_PTS
 }
 
 // d_n: bracket count in device memory (nullptr: n_max IS the count); n_max: launch bound (count known on the host, or the
@@ -1509,23 +1481,10 @@ int launch_refine(es_context* ctx, const es_problem* prob, const es_root_table& 
 int dispatch_refine(es_context* ctx, const es_problem* prob, const es_root_table& tab, const int* d_n, int n_max, int n_hint,
                     int n_bisect, double tol) {
   // the d_w / d_resid columns double as scratch for D at the two bracket ends until refinement overwrites them
-  switch (prob->dev.family) {
-    case FAM_CYL0: return launch_refine<FAM_CYL0>(ctx, prob, tab, tab.d_w, tab.d_resid, d_n, n_max, n_hint, n_bisect, tol);
-    case FAM_CYLT: return launch_refine<FAM_CYLT>(ctx, prob, tab, tab.d_w, tab.d_resid, d_n, n_max, n_hint, n_bisect, tol);
-    case FAM_SLABD: return launch_refine<FAM_SLABD>(ctx, prob, tab, tab.d_w, tab.d_resid, d_n, n_max, n_hint, n_bisect, tol);
-    case FAM_SLABF: return launch_refine<FAM_SLABF>(ctx, prob, tab, tab.d_w, tab.d_resid, d_n, n_max, n_hint, n_bisect, tol);
-    default: return ES_ERR_UNSUPPORTED;
-  }
+#define CALL_REFINE(F) launch_refine<F>(ctx, prob, tab, tab.d_w, tab.d_resid, d_n, n_max, n_hint, n_bisect, tol)
+  ES_DISPATCH_FAMILY(prob->dev.family, CALL_REFINE)
+#undef CALL_REFINE
 }
-
-#define ES_DISPATCH_FAMILY(fam, CALL)                      \
-  switch (fam) {                                           \
-    case FAM_CYL0: return CALL(FAM_CYL0);                  \
-    case FAM_CYLT: return CALL(FAM_CYLT);                  \
-    case FAM_SLABD: return CALL(FAM_SLABD);                \
-    case FAM_SLABF: return CALL(FAM_SLABF);                \
-    default: return ES_ERR_UNSUPPORTED;                    \
-  }
 
 }  // namespace
 
@@ -1771,9 +1730,7 @@ extern "C" int es_shoot_eval_points(es_context* ctx, const es_problem* prob, con
   if (n == 0) return ES_SUCCESS;
   ES_REQUIRE(ctx, d_k && d_w && d_D && d_status, "null pointer");
   ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-#define CALL_PTS(F) launch_points<F>(ctx, prob, d_k, d_w, n, d_D, d_rel, d_status)
-  ES_DISPATCH_FAMILY(prob->dev.family, CALL_PTS)
-#undef CALL_PTS
+  return dispatch_points(ctx, prob, d_k, d_w, nullptr, n, d_D, d_rel, d_status);
 }
 
 namespace {
@@ -1807,10 +1764,7 @@ int check_find_roots_args(es_context* ctx, const es_problem* prob, int nk, int n
   ES_REQUIRE(ctx, table, "null pointer");
   ES_REQUIRE(ctx, nk >= 0 && nw >= 0 && n_bisect >= 0 && table->capacity >= 0, "negative size");
   ES_REQUIRE(ctx, w_mode >= 0 && w_mode <= 2, "w_mode");
-  ES_REQUIRE(ctx, table->capacity == 0 || (table->d_k && table->d_w && table->d_w_lo && table->d_w_hi &&
-                                           table->d_resid && table->d_row && table->d_flag),
-             "null root table arrays");
-  return ES_SUCCESS;
+  return check_root_table(ctx, table);
 }
 }  // namespace
 
@@ -1951,14 +1905,6 @@ int launch_grid_f32(es_context* ctx, const es_problem* prob, const double* d_k, 
   }
 }
 
-template <int FAM>
-int points_into(es_context* ctx, const es_problem* prob, const double* pk, const double* pw, int n, double* pD,
-                uint8_t* pst) {
-  return launch_points<FAM>(ctx, prob, pk, pw, n, pD, nullptr, pst);
-}
-}  // namespace
-
-namespace {
 int check_mixed_args(es_context* ctx, const es_problem* prob, int nk, int nw, int w_mode) {
   int rc = check_problem(ctx, prob);
   if (rc) return rc;
@@ -1973,41 +1919,125 @@ int check_mixed_args(es_context* ctx, const es_problem* prob, int nk, int nw, in
   return ES_SUCCESS;
 }
 
-int launch_grid_f32_any(es_context* ctx, const es_problem* prob, const double* d_k, int nk, const double* d_w, int nw, int w_mode,
-                        double* d_D, uint8_t* d_status) {
-  switch (prob->dev.family) {
-    case FAM_CYL0: return launch_grid_f32<FAM_CYL0>(ctx, prob, d_k, nk, d_w, nw, w_mode, d_D, d_status);
-    case FAM_CYLT: return launch_grid_f32<FAM_CYLT>(ctx, prob, d_k, nk, d_w, nw, w_mode, d_D, d_status);
-    case FAM_SLABD: return launch_grid_f32<FAM_SLABD>(ctx, prob, d_k, nk, d_w, nw, w_mode, d_D, d_status);
-    default: return launch_grid_f32<FAM_SLABF>(ctx, prob, d_k, nk, d_w, nw, w_mode, d_D, d_status);
-  }
-}
-
-int points_any(es_context* ctx, const es_problem* prob, const double* pk, const double* pw, int n, double* pD, uint8_t* pst) {
-  switch (prob->dev.family) {
-    case FAM_CYL0: return points_into<FAM_CYL0>(ctx, prob, pk, pw, n, pD, pst);
-    case FAM_CYLT: return points_into<FAM_CYLT>(ctx, prob, pk, pw, n, pD, pst);
-    case FAM_SLABD: return points_into<FAM_SLABD>(ctx, prob, pk, pw, n, pD, pst);
-    default: return points_into<FAM_SLABF>(ctx, prob, pk, pw, n, pD, pst);
-  }
-}
-
-// fp64 points with the count in device memory, the launch sized for n_max points
-template <int FAM>
-int points_dcount(es_context* ctx, const es_problem* prob, const double* pk, const double* pw, const int* d_n, long n_max,
-                  double* pD, uint8_t* pst) {
-  hipLaunchKernelGGL((shoot_points_dcount_kernel<FAM>), dim3((unsigned)((n_max + 255) / 256)), dim3(256), 0, ctx->stream,
-                     prob->dev, pk, pw, d_n, pD, pst);
-  ES_HIP_CHECK(ctx, hipGetLastError());
+// The argument checks of the screened searches, before anything is enqueued or written, in two halves (the synchronous
+// call zeroes its host outputs between them).  `counts`: where the call reports its counts (h_count or d_counts).
+int check_screened_args(es_context* ctx, const es_problem* prob, int nk, int nw, int w_mode, int n_bisect,
+                        const es_root_table* table, const void* counts) {
+  int rc = check_mixed_args(ctx, prob, nk, nw, w_mode);
+  if (rc) return rc;
+  rc = check_refine_rule(ctx);
+  if (rc) return rc;
+  ES_REQUIRE(ctx, table && counts, "null pointer");
+  ES_REQUIRE(ctx, n_bisect >= 0 && table->capacity >= 0, "negative size");
+  ES_REQUIRE(ctx, table->capacity <= (1 << 30), "table capacity above 2^30 (the bracket-end count is an int32)");
   return ES_SUCCESS;
 }
 
-int points_dcount_any(es_context* ctx, const es_problem* prob, const double* pk, const double* pw, const int* d_n,
-                      long n_max, double* pD, uint8_t* pst) {
-  if (n_max <= 0) return ES_SUCCESS;
-#define CALL_PTS(F) points_dcount<F>(ctx, prob, pk, pw, d_n, n_max, pD, pst)
-  ES_DISPATCH_FAMILY(prob->dev.family, CALL_PTS)
-#undef CALL_PTS
+int check_screened_arrays(es_context* ctx, long cells, const double* d_k, const double* d_w, const double* d_D,
+                          const uint8_t* d_status, const es_root_table* table) {
+  if (cells == 0) return ES_SUCCESS;
+  ES_REQUIRE(ctx, d_k && d_w && d_D && d_status, "null pointer");
+  return check_root_table(ctx, table);
+}
+
+// The mixed search on a screened grid (everything of include/eigensolver_amd.h behind the fp32 march), arguments checked,
+// for the synchronous and the asynchronous entry points alike.  c[0 .. 3]: the count words (brackets, unsure points,
+// bracket-end points, unconfirmed brackets), device memory in both modes.
+//   h == nullptr, device-count mode (the asynchronous searches, c = the caller's d_counts): nothing is read back.  Every
+//     stage is launched for the grid or for the table capacity and reads its count from its word; the per-point scratch
+//     holds max(cells, 2 capacity) points.
+//   h != nullptr, host-count mode (es_shoot_find_roots_screened, c / h = the context's words and their pinned mirror): the
+//     total of each scan is read back into h and IS the launch bound of the stages that follow (d_n = nullptr) and the size
+//     of their scratch; a stage whose bound is 0 is skipped.  h[3] is read after the refinement is enqueued, with the last
+//     synchronisation of the call; h[2] is set on the host.
+int screened_search(es_context* ctx, const es_problem* prob, const double* d_k, int nk, const double* d_w, int nw,
+                    int w_mode, int n_bisect, double tol_percent, double* d_D, uint8_t* d_status,
+                    const es_root_table* table, int32_t* c, int32_t* h) {
+  const long cells = (long)nk * nw;
+  const int cap = table->capacity;
+  if (h) h[0] = h[1] = h[2] = h[3] = 0;
+  ES_HIP_CHECK(ctx, hipMemsetAsync(c, 0, 4 * sizeof(int32_t), ctx->stream));
+  if (cells == 0) return ES_SUCCESS;
+  int rc = es_ensure_scan_scratch(ctx, (size_t)cells);
+  if (rc) return rc;
+  // per-point scratch, 33 bytes per point; the unsure points and the bracket ends follow each other on the stream and
+  // share it
+  double *pk = nullptr, *pw = nullptr, *pD = nullptr; long* pcell = nullptr; uint8_t* pst = nullptr;
+  auto carve = [&](size_t npts) -> int {
+    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t bd = align(npts * sizeof(double));
+    const int r = es_ensure_scratch(ctx, 4 * bd + align(npts));
+    if (r) return r;
+    char* b = (char*)ctx->d_scratch;
+    pk = (double*)b; pw = (double*)(b + bd); pD = (double*)(b + 2 * bd); pcell = (long*)(b + 3 * bd);
+    pst = (uint8_t*)(b + 4 * bd);
+    return ES_SUCCESS;
+  };
+  auto read_back = [&](int word) -> int {
+    ES_HIP_CHECK(ctx, hipMemcpyAsync(h + word, c + word, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ES_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ES_SUCCESS;
+  };
+  const dim3 grid_blocks = es_blocks(cells);
+  if (!h && (rc = carve((size_t)cells > 2 * (size_t)cap ? (size_t)cells : 2 * (size_t)cap))) return rc;
+  // 1. flag the unsure points and scan: count to c[1]
+  hipLaunchKernelGGL(unsure_flag_kernel, grid_blocks, dim3(256), 0, ctx->stream, d_status, cells, ctx->d_masks,
+                     ctx->d_block_counts);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = es_scan_counts_async(ctx, ctx->d_block_counts, (int)grid_blocks.x, c + 1);
+  if (rc) return rc;
+  long n_pts = cells;                                            // bound of the unsure points
+  if (h) {
+    if ((rc = read_back(1))) return rc;
+    n_pts = h[1];
+    if (n_pts > 0 && (rc = carve((size_t)n_pts))) return rc;
+  }
+  // 2. gather them, re-evaluate in fp64, scatter back
+  if (n_pts > 0) {
+    hipLaunchKernelGGL(unsure_gather_kernel, grid_blocks, dim3(256), 0, ctx->stream, d_k, d_w, nw, w_mode, cells,
+                       ctx->d_masks, ctx->d_block_counts, pk, pw, pcell);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+    rc = dispatch_points(ctx, prob, pk, pw, h ? nullptr : c + 1, n_pts, pD, nullptr, pst);
+    if (rc) return rc;
+    hipLaunchKernelGGL(scatter_points_kernel, es_blocks(n_pts), dim3(256), 0, ctx->stream, pcell, pD, pst,
+                       h ? nullptr : c + 1, es_bound(n_pts), d_D, d_status);
+    ES_HIP_CHECK(ctx, hipGetLastError());
+  }
+  // 3. flag the brackets on the merged array (signs and statuses are now those of the fp64 path) and scan: count to c[0]
+  hipLaunchKernelGGL(bracket_flag_kernel, grid_blocks, dim3(256), 0, ctx->stream, d_D, d_status, nw, cells,
+                     ctx->d_masks, ctx->d_block_counts);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = es_scan_counts_async(ctx, ctx->d_block_counts, (int)grid_blocks.x, c);
+  if (rc) return rc;
+  int n_br = cap;                                                // bound of the brackets written and refined
+  if (h) {
+    if ((rc = read_back(0))) return rc;
+    if (h[0] < cap) n_br = h[0];
+  }
+  if (n_br == 0) return ES_SUCCESS;
+  const int* d_n = h ? nullptr : c;
+  // 4. emit the brackets, then both ends of every bracket in fp64: the refinement starts from the numbers of the fp64 path
+  hipLaunchKernelGGL(bracket_emit_kernel, grid_blocks, dim3(256), 0, ctx->stream, d_k, d_w, nw, w_mode, cells,
+                     d_D, ctx->d_masks, ctx->d_block_counts, *table, table->d_w, table->d_resid);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  if (h && (rc = carve(2 * (size_t)n_br))) return rc;
+  hipLaunchKernelGGL(bracket_end_points_kernel, es_blocks(n_br), dim3(256), 0, ctx->stream, *table, d_n, n_br, c + 2, pk, pw);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = dispatch_points(ctx, prob, pk, pw, h ? nullptr : c + 2, 2 * (long)n_br, pD, nullptr, pst);
+  if (rc) return rc;
+  hipLaunchKernelGGL(bracket_end_values_kernel, es_blocks(n_br), dim3(256), 0, ctx->stream, pD, pst, d_n, n_br, table->d_w,
+                     table->d_resid, c + 3);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  if (h) {
+    h[2] = 2 * n_br;
+    ES_HIP_CHECK(ctx, hipMemcpyAsync(h + 3, c + 3, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  // 5. refine in fp64; with the count on the device the launches are sized for the capacity and the expected count is
+  // half of it, as in es_shoot_find_roots_async
+  rc = dispatch_refine(ctx, prob, *table, d_n, n_br, h ? n_br : cap / 2, n_bisect, tol_percent);
+  if (rc) return rc;
+  if (h) ES_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return ES_SUCCESS;
 }
 }  // namespace
 
@@ -2020,7 +2050,37 @@ extern "C" int es_shoot_screen_grid(es_context* ctx, const es_problem* prob, con
   if ((long)nk * nw == 0) return ES_SUCCESS;
   ES_REQUIRE(ctx, d_k && d_w && d_D && d_status, "null pointer");
   ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return launch_grid_f32_any(ctx, prob, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+#define CALL_GRID_F32(F) launch_grid_f32<F>(ctx, prob, d_k, nk, d_w, nw, w_mode, d_D, d_status)
+  ES_DISPATCH_FAMILY(prob->dev.family, CALL_GRID_F32)
+#undef CALL_GRID_F32
+}
+
+// Steps 2 - 5 of the mixed search on a grid screened by es_shoot_screen_grid.
+extern "C" int es_shoot_find_roots_screened(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
+                                            const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
+                                            double* d_D, uint8_t* d_status, es_root_table* table, int* h_count,
+                                            int* h_stats) {
+  if (!ctx) return ES_ERR_INVALID_ARG;
+  int rc = check_screened_args(ctx, prob, nk, nw, w_mode, n_bisect, table, h_count);
+  if (rc) return rc;
+  *h_count = 0;
+  if (h_stats) h_stats[0] = h_stats[1] = h_stats[2] = 0;
+  const long cells = (long)nk * nw;
+  if (cells == 0) return ES_SUCCESS;
+  rc = check_screened_arrays(ctx, cells, d_k, d_w, d_D, d_status, table);
+  if (rc) return rc;
+  ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int32_t* h = ctx->h_screen;
+  rc = screened_search(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, tol_percent, d_D, d_status, table, ctx->d_screen,
+                       ctx->h_screen);
+  *h_count = h[0];
+  if (h_stats) { h_stats[0] = h[1]; h_stats[1] = h[2]; h_stats[2] = h[3]; }
+  if (rc) return rc;
+  if (h[3] != 0) {
+    ctx->last_error = "fp32 screening: a bracket was not confirmed by the fp64 values at its ends";
+    return ES_ERR_SCREENING;
+  }
+  return h[0] > table->capacity ? ES_ERR_CAPACITY : ES_SUCCESS;
 }
 
 extern "C" int es_shoot_find_roots_mixed(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
@@ -2033,208 +2093,32 @@ extern "C" int es_shoot_find_roots_mixed(es_context* ctx, const es_problem* prob
                                       h_count, h_stats);
 }
 
-// Steps 2 - 5 of the mixed search on a grid screened by es_shoot_screen_grid.
-extern "C" int es_shoot_find_roots_screened(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
-                                            const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
-                                            double* d_D, uint8_t* d_status, es_root_table* table, int* h_count,
-                                            int* h_stats) {
-  if (!ctx) return ES_ERR_INVALID_ARG;
-  int rc = check_mixed_args(ctx, prob, nk, nw, w_mode);
-  if (rc) return rc;
-  rc = check_refine_rule(ctx);
-  if (rc) return rc;
-  ES_REQUIRE(ctx, table && h_count, "null pointer");
-  ES_REQUIRE(ctx, n_bisect >= 0 && table->capacity >= 0, "negative size");
-  *h_count = 0;
-  if (h_stats) h_stats[0] = h_stats[1] = h_stats[2] = 0;
-  const long cells = (long)nk * nw;
-  if (cells == 0) return ES_SUCCESS;
-  ES_REQUIRE(ctx, d_k && d_w && d_D && d_status, "null pointer");
-  ES_REQUIRE(ctx, table->capacity == 0 || (table->d_k && table->d_w && table->d_w_lo && table->d_w_hi &&
-                                           table->d_resid && table->d_row && table->d_flag),
-             "null root table arrays");
-  ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // 2. unsure points -> fp64
-  rc = es_ensure_scan_scratch(ctx, (size_t)cells);
-  if (rc) return rc;
-  const int nblocks = (int)((cells + 255) / 256);
-  hipLaunchKernelGGL(unsure_flag_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_status, cells, ctx->d_masks,
-                     ctx->d_block_counts);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  int n_unsure = 0;
-  rc = es_scan_block_counts(ctx, nblocks, &n_unsure);
-  if (rc) return rc;
-  auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  auto carve = [&](size_t n, double*& pk, double*& pw, double*& pD, long*& pcell, uint8_t*& pst) -> int {
-    const size_t bd = align(n * sizeof(double));
-    int r = es_ensure_scratch(ctx, 4 * bd + align(n));
-    if (r) return r;
-    char* b = (char*)ctx->d_scratch;
-    pk = (double*)b; pw = (double*)(b + bd); pD = (double*)(b + 2 * bd); pcell = (long*)(b + 3 * bd);
-    pst = (uint8_t*)(b + 4 * bd);
-    return ES_SUCCESS;
-  };
-  double *pk, *pw, *pD; long* pcell; uint8_t* pst;
-  if (n_unsure > 0) {
-    rc = carve((size_t)n_unsure, pk, pw, pD, pcell, pst);
-    if (rc) return rc;
-    hipLaunchKernelGGL(unsure_gather_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_k, d_w, nw, w_mode, cells,
-                       ctx->d_masks, ctx->d_block_counts, pk, pw, pcell);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    rc = points_any(ctx, prob, pk, pw, n_unsure, pD, pst);
-    if (rc) return rc;
-    hipLaunchKernelGGL(scatter_points_kernel, dim3((n_unsure + 255) / 256), dim3(256), 0, ctx->stream, pcell, pD, pst,
-                       n_unsure, d_D, d_status);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-  }
-  // 3. brackets on the merged array (signs and statuses are now those of the fp64 path)
-  hipLaunchKernelGGL(bracket_flag_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_D, d_status, nw, cells,
-                     ctx->d_masks, ctx->d_block_counts);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  int total = 0;
-  rc = es_scan_block_counts(ctx, nblocks, &total);
-  if (rc) return rc;
-  *h_count = total;
-  const int n = total < table->capacity ? total : table->capacity;
-  int violations = 0;
-  if (n > 0) {
-    hipLaunchKernelGGL(bracket_emit_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_k, d_w, nw, w_mode, cells,
-                       d_D, ctx->d_masks, ctx->d_block_counts, *table, table->d_w, table->d_resid);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    // 4. both ends of every bracket in fp64: the refinement starts from the numbers of the fp64 path
-    rc = carve((size_t)2 * n, pk, pw, pD, pcell, pst);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bracket_ends_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, *table, n, pk, pw);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    rc = points_any(ctx, prob, pk, pw, 2 * n, pD, pst);
-    if (rc) return rc;
-    ES_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_total, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(bracket_ends_store_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pD, pst, n,
-                       table->d_w, table->d_resid, ctx->d_total);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    ES_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_total, ctx->d_total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    // 5. fp64 refinement
-    rc = dispatch_refine(ctx, prob, *table, nullptr, n, n, n_bisect, tol_percent);
-    if (rc) return rc;
-    ES_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    violations = *ctx->h_total;
-  }
-  if (h_stats) { h_stats[0] = n_unsure; h_stats[1] = 2 * n; h_stats[2] = violations; }
-  if (violations != 0) {
-    ctx->last_error = "fp32 screening: a bracket was not confirmed by the fp64 values at its ends";
-    return ES_ERR_SCREENING;
-  }
-  return total > table->capacity ? ES_ERR_CAPACITY : ES_SUCCESS;
-}
-
-// ---- steps 2 - 5 with the counts on the device (es_shoot_find_roots_screened_async / es_shoot_find_roots_mixed_async) ----
-namespace {
-// every argument check of the synchronous pair, before anything is enqueued
-int check_screened_async_args(es_context* ctx, const es_problem* prob, const double* d_k, int nk, const double* d_w,
-                              int nw, int w_mode, int n_bisect, const double* d_D, const uint8_t* d_status,
-                              const es_root_table* table, const int32_t* d_counts) {
-  int rc = check_mixed_args(ctx, prob, nk, nw, w_mode);
-  if (rc) return rc;
-  rc = check_refine_rule(ctx);
-  if (rc) return rc;
-  ES_REQUIRE(ctx, table && d_counts, "null pointer");
-  ES_REQUIRE(ctx, n_bisect >= 0 && table->capacity >= 0, "negative size");
-  ES_REQUIRE(ctx, table->capacity <= (1 << 30), "table capacity above 2^30 (the bracket-end count is an int32)");
-  if ((long)nk * nw == 0) return ES_SUCCESS;
-  ES_REQUIRE(ctx, d_k && d_w && d_D && d_status, "null pointer");
-  ES_REQUIRE(ctx, table->capacity == 0 || (table->d_k && table->d_w && table->d_w_lo && table->d_w_hi &&
-                                           table->d_resid && table->d_row && table->d_flag),
-             "null root table arrays");
-  return ES_SUCCESS;
-}
-
-// the launches of es_shoot_find_roots_screened with every count in d_counts (include/eigensolver_amd.h); arguments checked
-int screened_enqueue(es_context* ctx, const es_problem* prob, const double* d_k, int nk, const double* d_w, int nw,
-                     int w_mode, int n_bisect, double tol_percent, double* d_D, uint8_t* d_status,
-                     const es_root_table* table, int32_t* d_counts) {
-  const long cells = (long)nk * nw;
-  const int cap = table->capacity;
-  ES_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 4 * sizeof(int32_t), ctx->stream));
-  if (cells == 0) return ES_SUCCESS;
-  int rc = es_ensure_scan_scratch(ctx, (size_t)cells);
-  if (rc) return rc;
-  // per-point scratch for every cell (unsure points) or both ends of every record (bracket ends), whichever is more: the
-  // two uses follow each other on the stream and share the buffers (33 bytes per point, include/eigensolver_amd.h)
-  const size_t npts = (size_t)cells > 2 * (size_t)cap ? (size_t)cells : 2 * (size_t)cap;
-  auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t bd = align(npts * sizeof(double));
-  rc = es_ensure_scratch(ctx, 4 * bd + align(npts));
-  if (rc) return rc;
-  char* b = (char*)ctx->d_scratch;
-  double* pk = (double*)b;
-  double* pw = (double*)(b + bd);
-  double* pD = (double*)(b + 2 * bd);
-  long* pcell = (long*)(b + 3 * bd);
-  uint8_t* pst = (uint8_t*)(b + 4 * bd);
-  const int nblocks = (int)((cells + 255) / 256);
-  // 2. unsure points -> fp64: count to d_counts[1] (ctx->d_total is taken by the bracket scan below)
-  hipLaunchKernelGGL(unsure_flag_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_status, cells, ctx->d_masks,
-                     ctx->d_block_counts);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  rc = es_scan_block_counts_async(ctx, nblocks);
-  if (rc) return rc;
-  ES_HIP_CHECK(ctx, hipMemcpyAsync(d_counts + 1, ctx->d_total, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-  hipLaunchKernelGGL(unsure_gather_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_k, d_w, nw, w_mode, cells,
-                     ctx->d_masks, ctx->d_block_counts, pk, pw, pcell);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  rc = points_dcount_any(ctx, prob, pk, pw, d_counts + 1, cells, pD, pst);
-  if (rc) return rc;
-  hipLaunchKernelGGL(scatter_points_dcount_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, pcell, pD, pst,
-                     d_counts + 1, d_D, d_status);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  // 3. brackets on the merged array: count to d_counts[0]
-  hipLaunchKernelGGL(bracket_flag_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_D, d_status, nw, cells,
-                     ctx->d_masks, ctx->d_block_counts);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  rc = es_scan_block_counts_async(ctx, nblocks);
-  if (rc) return rc;
-  ES_HIP_CHECK(ctx, hipMemcpyAsync(d_counts, ctx->d_total, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-  if (cap == 0) return ES_SUCCESS;
-  hipLaunchKernelGGL(bracket_emit_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_k, d_w, nw, w_mode, cells,
-                     d_D, ctx->d_masks, ctx->d_block_counts, *table, table->d_w, table->d_resid);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  // 4. both ends of the first min(count, capacity) brackets in fp64; unconfirmed brackets to d_counts[3]
-  const dim3 cap_blocks((unsigned)((cap + 255) / 256));
-  hipLaunchKernelGGL(bracket_end_points_dcount_kernel, cap_blocks, dim3(256), 0, ctx->stream, *table, d_counts, pk, pw);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  rc = points_dcount_any(ctx, prob, pk, pw, d_counts + 2, 2 * (long)cap, pD, pst);
-  if (rc) return rc;
-  hipLaunchKernelGGL(bracket_end_values_dcount_kernel, cap_blocks, dim3(256), 0, ctx->stream, pD, pst, d_counts, cap,
-                     table->d_w, table->d_resid);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  // 5. fp64 refinement sized for the capacity, count from d_counts[0] (as es_shoot_find_roots_async)
-  return dispatch_refine(ctx, prob, *table, d_counts, cap, cap / 2, n_bisect, tol_percent);
-}
-}  // namespace
-
+// The same with the counts on the device: every check before anything is enqueued, nothing read back.
 extern "C" int es_shoot_find_roots_screened_async(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
                                                   const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
                                                   double* d_D, uint8_t* d_status, es_root_table* table,
                                                   int32_t* d_counts) {
   if (!ctx) return ES_ERR_INVALID_ARG;
-  int rc = check_screened_async_args(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, d_D, d_status, table, d_counts);
+  int rc = check_screened_args(ctx, prob, nk, nw, w_mode, n_bisect, table, d_counts);
+  if (rc) return rc;
+  rc = check_screened_arrays(ctx, (long)nk * nw, d_k, d_w, d_D, d_status, table);
   if (rc) return rc;
   ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return screened_enqueue(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, tol_percent, d_D, d_status, table, d_counts);
+  return screened_search(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, tol_percent, d_D, d_status, table, d_counts, nullptr);
 }
 
 extern "C" int es_shoot_find_roots_mixed_async(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
                                                const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
                                                double* d_D, uint8_t* d_status, es_root_table* table, int32_t* d_counts) {
   if (!ctx) return ES_ERR_INVALID_ARG;
-  int rc = check_screened_async_args(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, d_D, d_status, table, d_counts);
+  int rc = check_screened_args(ctx, prob, nk, nw, w_mode, n_bisect, table, d_counts);
+  if (rc) return rc;
+  rc = check_screened_arrays(ctx, (long)nk * nw, d_k, d_w, d_D, d_status, table);
+  if (rc) return rc;
+  rc = es_shoot_screen_grid(ctx, prob, d_k, nk, d_w, nw, w_mode, d_D, d_status);
   if (rc) return rc;
   ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if ((long)nk * nw > 0) {
-    rc = launch_grid_f32_any(ctx, prob, d_k, nk, d_w, nw, w_mode, d_D, d_status);
-    if (rc) return rc;
-  }
-  return screened_enqueue(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, tol_percent, d_D, d_status, table, d_counts);
+  return screened_search(ctx, prob, d_k, nk, d_w, nw, w_mode, n_bisect, tol_percent, d_D, d_status, table, d_counts, nullptr);
 }
 
 
@@ -2245,7 +2129,7 @@ __global__ __launch_bounds__(256) void pack_records_kernel(es_root_table tab, in
                                                            double* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;          // row of the send buffer: 0 = header, 1.. = records
   if (i > cap) return;
-  const int count = d_count ? *d_count : count_host;
+  const int count = es_count(d_count, count_host);       // the async call passes INT32_MAX: no cap on the count it reports
   double* o = out + (size_t)i * 6;
   int n = count < cap ? count : cap;                     // records written: the receiver compares the count with it
   if (n > tab.capacity) n = tab.capacity;
@@ -2286,7 +2170,7 @@ extern "C" int es_root_table_pack_async(es_context* ctx, const es_root_table* ta
   ES_REQUIRE(ctx, cap == 0 || (table->d_k && table->d_w && table->d_resid && table->d_row && table->d_flag),
              "null root table arrays");
   ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(pack_records_kernel, dim3((cap + 1 + 255) / 256), dim3(256), 0, ctx->stream, *table, 0, d_count, m,
+  hipLaunchKernelGGL(pack_records_kernel, dim3((cap + 1 + 255) / 256), dim3(256), 0, ctx->stream, *table, INT32_MAX, d_count, m,
                      d_rows_global, cap, d_out);
   ES_HIP_CHECK(ctx, hipGetLastError());
   return ES_SUCCESS;

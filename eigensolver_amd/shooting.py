@@ -111,13 +111,16 @@ class ShootProblem:
             return a.to(device=dev, dtype=torch.float64).contiguous()
         return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
 
+    def _grid_args(self, k, w, w_mode):
+        """(dk, dw, nk, nw): k and omega on the device and the grid size, as every grid entry point takes them."""
+        dk, dw = self._dev(k).reshape(-1), self._dev(w)
+        return dk, dw, dk.numel(), dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+
     def eval_grid(self, k, w, w_mode=W_PHASE_SPEED, want_rel=False, skip_continuum=False):
         """D[ik, iw], status[ik, iw] (and rel) on the (k, omega) grid; w_mode selects how omega is formed.
         skip_continuum: ES_EVAL_SKIP_CONTINUUM -- points inside a continuum band get D = NaN and are not marched."""
         import torch
-        dk, dw = self._dev(k).reshape(-1), self._dev(w)
-        nk = dk.numel()
-        nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+        dk, dw, nk, nw = self._grid_args(k, w, w_mode)
         if w_mode == W_PER_ROW:
             assert dw.numel() == nk * nw
         D = torch.empty((nk, nw), dtype=torch.float64, device=dk.device)
@@ -184,9 +187,7 @@ class ShootProblem:
     def find_roots(self, k, w, D, status, w_mode=W_PHASE_SPEED, n_bisect=40, tol_percent=1e-3, capacity=None,
                    table=None):
         """Brackets + bisection + classification on the grid evaluated by eval_grid. Returns (dict, count)."""
-        dk, dw = self._dev(k).reshape(-1), self._dev(w)
-        nk = dk.numel()
-        nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+        dk, dw, nk, nw = self._grid_args(k, w, w_mode)
         cap = int(capacity) if capacity is not None else max(1024, 16 * nk)
         while True:
             t, rt = table if table is not None else self.alloc_root_table(cap)
@@ -205,9 +206,7 @@ class ShootProblem:
         """es_shoot_find_roots_async: everything enqueued on the context's stream, nothing read back.  `table` is
         (dict, RootTable) from alloc_root_table, `count` an int32 CUDA tensor of one element that receives the bracket
         count (it may exceed the capacity: check when reading it).  Returns the full-capacity dict of the table."""
-        dk, dw = self._dev(k).reshape(-1), self._dev(w)
-        nk = dk.numel()
-        nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+        dk, dw, nk, nw = self._grid_args(k, w, w_mode)
         t, rt = table
         assert count.is_cuda and count.numel() == 1 and count.element_size() == 4
         rc = self.ctx.lib.es_shoot_find_roots_async(self.ctx.handle, self.handle, _lib.ptr(dk), nk, _lib.ptr(dw), nw,
@@ -220,9 +219,7 @@ class ShootProblem:
         """Step 1 of the mixed search alone (es_shoot_screen_grid): the fp32 screening march, enqueued.  Returns the
         screened (D, status) for find_roots_screened."""
         import torch
-        dk, dw = self._dev(k).reshape(-1), self._dev(w)
-        nk = dk.numel()
-        nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+        dk, dw, nk, nw = self._grid_args(k, w, w_mode)
         D = torch.empty((nk, nw), dtype=torch.float64, device=dk.device)
         st = torch.empty((nk, nw), dtype=torch.uint8, device=dk.device)
         rc = self.ctx.lib.es_shoot_screen_grid(self.ctx.handle, self.handle, _lib.ptr(dk), nk, _lib.ptr(dw), nw, w_mode,
@@ -232,9 +229,7 @@ class ShootProblem:
 
     def find_roots_screened(self, k, w, D, st, w_mode=W_PHASE_SPEED, n_bisect=40, tol_percent=1e-3, table=None, capacity=None):
         """Steps 2 - 5 of the mixed search on a grid screened by screen_grid; returns what find_roots_mixed returns."""
-        dk, dw = self._dev(k).reshape(-1), self._dev(w)
-        nk = dk.numel()
-        nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+        dk, dw, nk, nw = self._grid_args(k, w, w_mode)
         t, rt = table if table is not None else self.alloc_root_table(int(capacity) if capacity is not None else max(1024, 16 * nk))
         n = C.c_int(0)
         stats = (C.c_int * 3)()
@@ -250,9 +245,7 @@ class ShootProblem:
         fp64 refinement (es_shoot_find_roots_mixed).  Returns (root dict, bracket count, D, status, stats) with
         stats = (fp64 re-evaluations of unsure grid points, of bracket ends, unconfirmed brackets)."""
         import torch
-        dk, dw = self._dev(k).reshape(-1), self._dev(w)
-        nk = dk.numel()
-        nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+        dk, dw, nk, nw = self._grid_args(k, w, w_mode)
         D = torch.empty((nk, nw), dtype=torch.float64, device=dk.device)
         st = torch.empty((nk, nw), dtype=torch.uint8, device=dk.device)
         cap = int(capacity) if capacity is not None else max(1024, 16 * nk)
@@ -283,9 +276,7 @@ class ShootProblem:
         import torch
         self._check_counts(counts)
         with torch.cuda.stream(self.ctx.torch_stream):      # temporaries are released to the context's stream
-            dk, dw = self._dev(k).reshape(-1), self._dev(w)
-            nk = dk.numel()
-            nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+            dk, dw, nk, nw = self._grid_args(k, w, w_mode)
             t, rt = table
             rc = self.ctx.lib.es_shoot_find_roots_screened_async(self.ctx.handle, self.handle, _lib.ptr(dk), nk, _lib.ptr(dw),
                                                                  nw, w_mode, int(n_bisect), float(tol_percent), _lib.ptr(D),
@@ -299,9 +290,7 @@ class ShootProblem:
         import torch
         self._check_counts(counts)
         with torch.cuda.stream(self.ctx.torch_stream):
-            dk, dw = self._dev(k).reshape(-1), self._dev(w)
-            nk = dk.numel()
-            nw = dw.shape[-1] if w_mode == W_PER_ROW else dw.numel()
+            dk, dw, nk, nw = self._grid_args(k, w, w_mode)
             D = torch.empty((nk, nw), dtype=torch.float64, device=dk.device)
             st = torch.empty((nk, nw), dtype=torch.uint8, device=dk.device)
             t, rt = table

@@ -266,9 +266,13 @@ int es_shoot_find_roots_screened(es_context* ctx, const es_problem* prob, const 
  *   [3] brackets whose fp64 ends do not confirm them                                    (h_stats[2]; the synchronous call
  *       returns ES_ERR_SCREENING)
  * For the same inputs d_D, d_status and the root table are those of es_shoot_screen_grid + es_shoot_find_roots_screened, bit
- * for bit (the first `capacity` records when [0] > capacity).  Every launch is sized for the grid (nk * nw) or for the
- * table capacity and takes its count from d_counts; size the table for the data (about twice the expected count), as for
- * es_shoot_find_roots_async.  Nothing is copied to the host and nothing is synchronised, except that a call which grows the
+ * for bit (the first `capacity` records when [0] > capacity): the synchronous and the asynchronous calls are one pipeline
+ * of the same kernels, which all take a count as (d_n, n_max) -- the launch is sized for n_max, the count is min(*d_n, n_max)
+ * read on the device, or n_max when d_n is null.  The synchronous call keeps the four words in the context, reads each
+ * count back after its scan and launches the next stages for exactly that many (d_n null); here every launch is sized for
+ * the grid (nk * nw) or for the table capacity and takes its count from d_counts.  Size the table for the data (about twice
+ * the expected count), as for es_shoot_find_roots_async; a capacity above 2^30 is an argument error in all four calls (the
+ * bracket-end count is an int32).  Nothing is copied to the host and nothing is synchronised, except that a call which grows the
  * context's scratch (the first one at a larger grid or table capacity) frees and allocates device memory, and hipFree /
  * hipMalloc synchronise.  Scratch of the context: 33 bytes per point for max(nk * nw, 2 capacity) points, plus the
  * bracket-scan scratch of 1/8 + 1/64 bytes per grid cell.

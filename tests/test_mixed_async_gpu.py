@@ -32,10 +32,10 @@ def _same_records(ta, tb, n):
         assert _bits(ta[name][:n]) == _bits(tb[name][:n]), name
 
 
-def _sync_screened(gp, dk, dW, D, st, cap):
+def _sync_screened(gp, dk, dW, D, st, cap, table=None):
     """es_shoot_find_roots_screened called directly: (status, table dict, h_count, h_stats), ES_ERR_SCREENING included."""
     from eigensolver_amd import _lib
-    t, rt = gp.alloc_root_table(cap)
+    t, rt = table if table is not None else gp.alloc_root_table(cap)
     n = C.c_int(0)
     stats = (C.c_int * 3)()
     rc = gp.ctx.lib.es_shoot_find_roots_screened(gp.ctx.handle, gp.handle, _lib.ptr(dk), dk.numel(), _lib.ptr(dW),
@@ -85,6 +85,91 @@ def test_mixed_async_equals_mixed(es_ctx, name):
     assert n > 0 and tuple(counts.cpu().tolist()) == (n, *stats)
     assert _bits(Da) == _bits(Ds) and _bits(sta) == _bits(sts)
     _same_records(rs, ta, n)
+    gp.close()
+
+
+@pytest.mark.parametrize("name", ["CF_flow_kink", "SD_w15_kink"])
+def test_no_unsure_points(es_ctx, name):
+    """The unsure bit cleared at every point before the screened call: the synchronous call skips the re-evaluation stage,
+    the async call runs it with a device count of 0, and neither touches D or status.  The brackets are then those of the
+    fp32 values, so the synchronous call may return 0 or ES_ERR_SCREENING; the async counts[3] is its h_stats[2]."""
+    import torch
+    from eigensolver_amd import ShootProblem
+    eq, mode, m, dk, dW = _grid(name)
+    gp = ShootProblem(eq, mode, m, ctx=es_ctx)
+    D0, st0 = gp.screen_grid(dk, dW)
+    st0 = st0 & 0x7F
+    cap = 1 << 16
+    Ds, sts, Da, sta = D0.clone(), st0.clone(), D0.clone(), st0.clone()
+    rc, ts, hc, hs = _sync_screened(gp, dk, dW, Ds, sts, cap)
+    assert rc == (7 if hs[2] else 0) and 0 < hc <= cap, (rc, hc, hs)
+    counts = _counts()
+    ta = gp.find_roots_screened_async(dk, dW, Da, sta, gp.alloc_root_table(cap), counts, n_bisect=N_BISECT)
+    torch.cuda.synchronize()
+    assert _bits(Ds) == _bits(D0) and _bits(sts) == _bits(st0)
+    assert _bits(Da) == _bits(Ds) and _bits(sta) == _bits(sts)
+    c = tuple(counts.cpu().tolist())
+    assert c == (hc, *hs) and c[1] == 0 and c[3] == hs[2], (c, hc, hs)
+    _same_records(ts, ta, hc)
+    gp.close()
+
+
+@pytest.mark.parametrize("name", ["CF_flow_kink", "SD_w15_kink"])
+def test_capacity_zero(es_ctx, name):
+    """A root table of capacity 0 with null arrays: both calls count the unsure points and the brackets and stop there."""
+    import torch
+    from eigensolver_amd import ShootProblem, _lib
+    eq, mode, m, dk, dW = _grid(name)
+    gp = ShootProblem(eq, mode, m, ctx=es_ctx)
+    D0, st0 = gp.screen_grid(dk, dW)
+    rc, _, n, stats = _sync_screened(gp, dk, dW, D0.clone(), st0.clone(), 1 << 16)
+    assert rc == 0 and n > 0 and stats[0] > 0, (rc, n, stats)
+    null = ({}, _lib.RootTable(None, None, None, None, None, None, None, 0))
+    Ds, sts, Da, sta = D0.clone(), st0.clone(), D0.clone(), st0.clone()
+    rc, _, hc, hs = _sync_screened(gp, dk, dW, Ds, sts, 0, table=null)
+    assert rc == 3 and hc == n and hs == (stats[0], 0, 0), (rc, hc, hs)
+    counts = _counts()
+    gp.find_roots_screened_async(dk, dW, Da, sta, null, counts, n_bisect=N_BISECT)
+    torch.cuda.synchronize()
+    assert tuple(counts.cpu().tolist()) == (n, stats[0], 0, 0)
+    assert _bits(Da) == _bits(Ds) and _bits(sta) == _bits(sts)
+    gp.close()
+
+
+@pytest.mark.parametrize("name", ["CF_flow_kink", "SD_w15_kink"])
+def test_eval_points_bounds(es_ctx, name):
+    """es_shoot_eval_points on the first n of 513 points, n around the 256 points of a workgroup, with and without d_rel:
+    the first n outputs are those of the n = 513 call bit for bit and nothing is written from element n on."""
+    import torch
+    from tests import cases
+    from eigensolver_amd import ShootProblem, _lib
+    eq, mode, m, (lo, hi) = cases.all_cases()[name]
+    gp = ShootProblem(eq, mode, m, ctx=es_ctx)
+    N, SENT, SENT_ST = 513, -12345.678, 0xA5
+    k = np.linspace(0.3, 3.4, N)
+    dk = torch.as_tensor(k, device="cuda")
+    dw = torch.as_tensor(k * (lo + (np.arange(N) + 0.5) * (hi - lo) / N), device="cuda")
+
+    def call(n, want_rel):
+        D = torch.full((N,), SENT, dtype=torch.float64, device="cuda")
+        rel = torch.full((N,), SENT, dtype=torch.float64, device="cuda")
+        st = torch.full((N,), SENT_ST, dtype=torch.uint8, device="cuda")
+        rc = es_ctx.lib.es_shoot_eval_points(es_ctx.handle, gp.handle, _lib.ptr(dk), _lib.ptr(dw), n, _lib.ptr(D),
+                                             _lib.ptr(rel) if want_rel else None, _lib.ptr(st))
+        assert rc == 0
+        torch.cuda.synchronize()
+        return D, rel, st
+
+    Df, relf, stf = call(N, True)
+    assert (stf == 0).any() and SENT_ST not in stf.cpu().tolist()
+    sent_d, sent_st = torch.full((N,), SENT, dtype=torch.float64), torch.full((N,), SENT_ST, dtype=torch.uint8)
+    for n in (1, 255, 256, 257, 513):
+        for want_rel in (True, False):
+            D, rel, st = call(n, want_rel)
+            assert _bits(D[:n]) == _bits(Df[:n]) and _bits(st[:n]) == _bits(stf[:n]), (n, want_rel)
+            assert _bits(D[n:]) == _bits(sent_d[n:]) and _bits(st[n:]) == _bits(sent_st[n:]), (n, want_rel)
+            nr = n if want_rel else 0
+            assert _bits(rel[:nr]) == _bits(relf[:nr]) and _bits(rel[nr:]) == _bits(sent_d[nr:]), (n, want_rel)
     gp.close()
 
 
