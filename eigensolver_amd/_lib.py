@@ -175,6 +175,19 @@ class ComplexRootTable(C.Structure):
                 ("d_row", C.c_void_p), ("d_flag", C.c_void_p), ("capacity", C.c_int32)]
 
 
+# ---- perturbation fields (include/eigensolver_amd.h section 7) -------------------------------------------------
+_FIELD_PROFILE_FIELDS = ("r", "rho", "Bz", "Bphi", "vz", "vphi", "bA", "qc", "q", "s_phi", "s_z")
+
+
+class FieldProfiles(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _FIELD_PROFILE_FIELDS]
+
+
+AMP_NAMES = ("xi_r", "xi_phi", "xi_z", "P_T", "v_r", "v_phi", "v_z")                       # ES_AMP_*
+VAR_NAMES = ("xi_r", "xi_phi", "P_T", "v_r", "v_phi", "xi_x", "xi_y", "v_x", "v_y", "v_z", "xi_z")   # ES_VAR_* (mask bits)
+FIELD_REFERENCE, FIELD_Z_REFERENCE_ANGLE, FIELD_BIG_ENDIAN = 1, 2, 4
+
+
 def _sig(lib):
     """Argument / result types of every entry point of include/eigensolver_amd.h (sections in header order)."""
     vp, i, d = C.c_void_p, C.c_int, C.c_double
@@ -228,4 +241,8 @@ def _sig(lib):
     lib.es_complex_find_roots.argtypes = [vp, vp, i, vp, i, vp, i, vp, i, i, vp, vp, vp, i, d,
                                           C.POINTER(ComplexRootTable), C.POINTER(i)]
     lib.es_complex_eigenfunction.argtypes = [vp, vp, i, vp, vp, vp, i, vp, vp, i, vp, vp, vp, vp]
+    # (7) perturbation fields
+    lib.es_cyl_polarisation.argtypes = [vp, vp, vp, i, i, vp, vp, i, vp, vp, vp, C.POINTER(FieldProfiles), i, d, d, d, d,
+                                        i, vp, vp]
+    lib.es_cyl_field_synthesis.argtypes = [vp, vp, vp, i, i, d, d, vp, i, vp, i, vp, i, C.c_uint32, d, i, vp, vp]
     return lib

@@ -93,6 +93,18 @@ class _CylinderBase:
     def rdC3(self, r):
         return np.zeros_like(r)
 
+    # closed-form shear terms of the perturbation fields (Export_vtk.py:798-799, :812-813; ShootProblem.polarisation)
+    def dv_z_dr(self, r):
+        return np.zeros_like(r)
+
+    def dv_z_over_r_dr(self, r):
+        """d(v_z/r)/dr, what the export scripts differentiate (`sym.diff(v_iz(r)/r)`)."""
+        return np.zeros_like(r)
+
+    def dv_phi_over_r_dr(self, r):
+        """d(v_phi/r)/dr (`sym.diff(v_iphi(r)/r)`)."""
+        return np.zeros_like(r)
+
     twisted = False
 
     def bc_const(self, axis_bc):
@@ -130,6 +142,13 @@ class CylinderFlow(_CylinderBase):
     def v_z(self, r):
         return self.U_e + (self.U_i0 - self.U_e) * np.exp(-(r - self.r0) ** 2 / self.width ** 2)
 
+    def dv_z_dr(self, r):
+        g = np.exp(-(r - self.r0) ** 2 / self.width ** 2)
+        return (self.U_i0 - self.U_e) * g * (-2.0 * (r - self.r0) / self.width ** 2)
+
+    def dv_z_over_r_dr(self, r):
+        return self.dv_z_dr(r) / r - self.v_z(r) / r ** 2
+
 
 @dataclass
 class CylinderRotation(_CylinderBase):
@@ -144,6 +163,9 @@ class CylinderRotation(_CylinderBase):
 
     def v_phi(self, r):
         return self.v_twist * r ** self.power
+
+    def dv_phi_over_r_dr(self, r):
+        return self.v_twist * (self.power - 1.0) * r ** (self.power - 2.0)
 
     def c2(self, r):
         P_0 = self.c_i0 ** 2 * self.rho_i0 / GAMMA                                       # CR-KF:128

@@ -100,3 +100,67 @@ def write_vtk(dump_file, x, y, z, variables, names):
             f.write(b"LOOKUP_TABLE default \n")
             f.write(packed(var).tobytes())
     return str(dump_file) + ".vtk"
+
+
+def _payload(a):
+    """bytes of an already-packed big-endian payload: bytes-like, a NumPy array or a CPU torch tensor (any dtype: its
+    memory is written as it stands)."""
+    if isinstance(a, (bytes, bytearray, memoryview)):
+        return a
+    if hasattr(a, "detach"):                     # torch tensor
+        if a.is_cuda:
+            raise ValueError("packed payloads must be in host memory (tensor.cpu())")
+        a = a.detach().contiguous().numpy()
+    return np.ascontiguousarray(a).tobytes()
+
+
+def write_vtk_packed(dump_file, dims, points_be, variables_be, names):
+    """`write_vtk` for payloads that are already packed: the same header lines around big-endian float32 buffers in VTK's
+    point order (first index fastest), e.g. what ShootProblem.fields(..., big_endian=True) produces on the GPU.
+    dims = (ax, ay, az); points_be holds ax*ay*az interleaved (x, y, z) triples, every entry of variables_be ax*ay*az
+    values.  Byte for byte the file write_vtk gives for the same numbers.  Writes `<dump_file>.vtk`."""
+    ax, ay, az = (int(v) for v in dims)
+    n = ax * ay * az
+    if len(variables_be) != len(names):
+        raise ValueError("one name per variable")
+    pts = _payload(points_be)
+    if len(pts) != 12 * n:
+        raise ValueError(f"points payload has {len(pts)} bytes, the grid needs {12 * n}")
+    with open(str(dump_file) + ".vtk", "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0 \n")
+        f.write(b"vtk output \n")
+        f.write(b"BINARY \n")
+        f.write(b"DATASET STRUCTURED_GRID \n")
+        f.write(("DIMENSIONS  %s %s %s  \n" % (ax, ay, az)).encode())
+        f.write(("POINTS %s float  \n" % n).encode())
+        f.write(pts)
+        f.write(("\nPOINT_DATA %s  " % n).encode())
+        for name, var in zip(names, variables_be):
+            buf = _payload(var)
+            if len(buf) != 4 * n:
+                raise ValueError(f"variable {name!r} has {len(buf)} bytes, the grid needs {4 * n}")
+            f.write(("\nSCALARS %s float \n" % name).encode())
+            f.write(b"LOOKUP_TABLE default \n")
+            f.write(buf)
+    return str(dump_file) + ".vtk"
+
+
+def write_vtk_frames(prefix, fields_iter, names=None):
+    """One legacy-VTK file per frame from ShootProblem.fields(..., big_endian=True): `<prefix><t>.vtk` with t the frame
+    number counted over all chunks, the naming of Export_vtk.py:989.  fields_iter is the dict `fields` returns or the
+    generator it returns with frames_per_call; names defaults to the variables of the chunks.  Each chunk is copied to
+    the host once.  Returns the list of files written."""
+    if isinstance(fields_iter, dict):
+        fields_iter = [fields_iter]
+    files, frame, pts = [], 0, None
+    for chunk in fields_iter:
+        use = list(chunk["names"]) if names is None else list(names)
+        if pts is None:
+            n_z, n_theta, n_r = chunk["points"].shape[:3]
+            pts = chunk["points"].cpu()
+        host = {v: chunk[v].cpu() for v in use}
+        for i in range(chunk["frames"].shape[0]):
+            files.append(write_vtk_packed(str(prefix) + str(frame), (n_r, n_theta, n_z), pts,
+                                          [host[v][i] for v in use], use))
+            frame += 1
+    return files

@@ -39,6 +39,62 @@ def read_screen_counts(counts, capacity):
     return r
 
 
+def var_mask(variables):
+    """Mask of es_cyl_field_synthesis and the names in the order it stores them (ascending bit, _lib.VAR_NAMES)."""
+    names = list(_lib.VAR_NAMES) if variables is None else list(variables)
+    unknown = [v for v in names if v not in _lib.VAR_NAMES]
+    if unknown:
+        raise ValueError(f"unknown field variable(s) {unknown}: choose from {_lib.VAR_NAMES}")
+    mask = 0
+    for v in names:
+        mask |= 1 << _lib.VAR_NAMES.index(v)
+    return mask, [v for b, v in enumerate(_lib.VAR_NAMES) if (mask >> b) & 1]
+
+
+def field_profiles(eq, r, reference_quirks=True):
+    """The es_field_profiles arrays of cylinder equilibrium `eq` at the radii r (> 0) as NumPy arrays, formed as
+    es_problem_create forms the determinant's (bA = B_z/sqrt(rho), qc = c^2/(c^2 + vA^2) with vA as written, CF:173-174).
+    reference_quirks: q is the constant c_i0^2/(c_i0^2 + vA_i0^2) and s_z = d(v_z/r)/dr, as the export scripts write
+    them (Export_vtk.py:780, :812-813); otherwise the local ratio and dv_z/dr."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    rho, Bz, Bphi, c2 = eq.rho(r), eq.B_z(r), eq.B_phi(r), eq.c2(r)
+    sr = np.sqrt(rho)
+    vA = (Bz + Bphi) / sr
+    qc = c2 / (c2 + vA * vA)
+    out = dict(r=r, rho=rho, Bz=Bz, Bphi=Bphi, vz=eq.v_z(r), vphi=eq.v_phi(r), bA=Bz / sr, qc=qc,
+               s_phi=eq.dv_phi_over_r_dr(r))
+    if reference_quirks:
+        out["q"] = np.full_like(r, eq.c_i0 ** 2 / (eq.c_i0 ** 2 + eq.vA_i0 ** 2))
+        out["s_z"] = eq.dv_z_over_r_dr(r)
+    else:
+        out["q"] = qc
+        out["s_z"] = eq.dv_z_dr(r)
+    return {n: np.ascontiguousarray(out[n], dtype=np.float64) for n in _lib._FIELD_PROFILE_FIELDS}
+
+
+def field_synthesis(ctx, radius, amp, m, k, w, theta, z, t, variables=None, v_scale=1.0, flags=0, want_points=True,
+                    out=None):
+    """es_cyl_field_synthesis for the amplitude table of one mode (radius [n_r], amp [7, n_r], CUDA float64): float32
+    frames out[n_t, n_sel, n_z, n_theta, n_r] in the order of var_mask(variables)[1] and, with want_points, the mesh
+    points[n_z, n_theta, n_r, 3].  theta, z, t: CUDA float64 vectors.  `out`: a preallocated contiguous float32 tensor
+    of that shape (4-byte alignment suffices).  Enqueued on the context's stream; returns (out, points, names)."""
+    import torch
+    mask, names = var_mask(variables)
+    n_r, n_theta, n_z, n_t = radius.numel(), theta.numel(), z.numel(), t.numel()
+    assert amp.shape == (7, n_r) and amp.dtype == torch.float64 and radius.dtype == torch.float64
+    shape = (n_t, len(names), n_z, n_theta, n_r)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=radius.device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous()
+    pts = torch.empty((n_z, n_theta, n_r, 3), dtype=torch.float32, device=radius.device) if want_points else None
+    rc = ctx.lib.es_cyl_field_synthesis(ctx.handle, _lib.ptr(radius), _lib.ptr(amp), n_r, int(m), float(k), float(w),
+                                        _lib.ptr(theta), n_theta, _lib.ptr(z), n_z, _lib.ptr(t), n_t, mask,
+                                        float(v_scale), int(flags), _lib.ptr(pts) if want_points else None,
+                                        _lib.ptr(out))
+    _lib.check(ctx.handle, rc)
+    return out, pts, names
+
+
 def make_desc(eq, mode, m=None):
     """es_shoot_desc + profile dict for equilibrium `eq` and mode "kink" / "sausage" (azimuthal order m for
     cylinders defaults to the reference's 1 / 0)."""
@@ -173,6 +229,81 @@ class ShootProblem:
         _lib.check(self.ctx.handle, rc)
         x_int = torch.linspace(self.desc.x_boundary, self.desc.x_end, N, dtype=torch.float64, device=dev)
         return dict(x_int=x_int, value_int=vi, flux_int=fi, x_ext=xe, value_ext=ve, flux_ext=fe)
+
+    def _require_positive_cylinder(self):
+        if not isinstance(self.eq, eqm._CylinderBase):
+            raise ValueError("perturbation fields exist for cylinders only (the reference has no slab movies)")
+        if self.desc.x_boundary < 0:
+            raise ValueError("perturbation fields need positive radii: build the equilibrium with r_sign=+1")
+
+    def field_profiles(self, reference_quirks=True):
+        """field_profiles(eq, r, ...) at this problem's interior nodes (node 0 = boundary)."""
+        self._require_positive_cylinder()
+        return field_profiles(self.eq, self._prof_np["r"][::2], reference_quirks)
+
+    def polarisation(self, k, w, n_ext=500, reference_quirks=True):
+        """Radial amplitudes of the modes at the (k, omega) pairs (es_cyl_polarisation on the arrays of `eigenfunction`):
+        dict of CUDA tensors radius [n, N + n_ext] and amp [n, 7, N + n_ext], channels _lib.AMP_NAMES, on the
+        reference's grid concatenate(ix[::-1], lx[::-1]).  A pair that is not ES_PT_OK gets NaN amplitudes."""
+        import torch
+        self._require_positive_cylinder()
+        e = self.eigenfunction(k, w, n_ext=n_ext)
+        dk, dw = self._dev(k).reshape(-1), self._dev(w).reshape(-1)
+        n, N = dk.numel(), int(self.desc.n_nodes)
+        prof = {a: self._dev(b) for a, b in self.field_profiles(reference_quirks).items()}
+        fp = _lib.FieldProfiles(*[prof[a].data_ptr() for a in _lib._FIELD_PROFILE_FIELDS])
+        radius = torch.empty((n, N + n_ext), dtype=torch.float64, device=dk.device)
+        amp = torch.empty((n, 7, N + n_ext), dtype=torch.float64, device=dk.device)
+        d = self.desc
+        rc = self.ctx.lib.es_cyl_polarisation(self.ctx.handle, _lib.ptr(dk), _lib.ptr(dw), n, N,
+                                              _lib.ptr(e["value_int"]), _lib.ptr(e["flux_int"]), int(n_ext),
+                                              _lib.ptr(e["x_ext"]), _lib.ptr(e["value_ext"]), _lib.ptr(e["flux_ext"]),
+                                              C.byref(fp), int(d.m), d.rho_e, d.vA_e, d.c_e, d.cT_e,
+                                              _lib.FIELD_REFERENCE if reference_quirks else 0, _lib.ptr(radius),
+                                              _lib.ptr(amp))
+        _lib.check(self.ctx.handle, rc)
+        return dict(radius=radius, amp=amp)
+
+    def fields(self, k, w, theta, z, t, variables=None, v_scale=1.0, big_endian=False, frames_per_call=None, n_ext=500,
+               reference_quirks=True):
+        """Perturbation fields of ONE root (k, omega) on the mesh (r, theta, z, t): float32 CUDA tensors in VTK's point
+        order (Export_vtk.py:930-950 on the GPU).  Returns a dict
+            points [n_z, n_theta, n_r, 3], t [n_t], names, frames [n_t, n_sel, n_z, n_theta, n_r], <name>: frames[:, i]
+        with r on polarisation's grid; `variables` defaults to all of _lib.VAR_NAMES and is stored in that order.
+        frames_per_call: a generator of such dicts, at most that many frames each (the frames tensor of a chunk is
+        released with its dict, so a long movie never holds more than one chunk on the device).
+        reference_quirks: the export scripts as written, -sin(m theta) on the z-components included; v_scale multiplies
+        every velocity.  big_endian: every float32 is byte-swapped on the device, ready for postprocess.write_vtk_frames."""
+        import torch
+        self._require_positive_cylinder()
+        if np.ndim(k) != 0 or np.ndim(w) != 0:
+            raise ValueError("fields() takes one root: scalar k and omega")
+        mask, names = var_mask(variables)
+        pol = self.polarisation([float(k)], [float(w)], n_ext=n_ext, reference_quirks=reference_quirks)
+        radius, amp = pol["radius"][0], pol["amp"][0]
+        dth, dz, dt = (self._dev(a).reshape(-1) for a in (theta, z, t))
+        flags = (_lib.FIELD_Z_REFERENCE_ANGLE if reference_quirks else 0) | (_lib.FIELD_BIG_ENDIAN if big_endian else 0)
+
+        def chunk(t_part, points):
+            out, pts, _ = field_synthesis(self.ctx, radius, amp, int(self.desc.m), k, w, dth, dz, t_part, names, v_scale,
+                                          flags, want_points=points is None)
+            d = dict(points=pts if points is None else points, t=t_part, names=names, frames=out)
+            d.update({v: out[:, i] for i, v in enumerate(names)})
+            return d
+
+        if frames_per_call is None:
+            return chunk(dt, None)
+        step = int(frames_per_call)
+        if step < 1:
+            raise ValueError("frames_per_call must be >= 1")
+
+        def chunks():
+            points = None
+            for a in range(0, dt.numel(), step):
+                d = chunk(dt[a:a + step], points)
+                points = d["points"]
+                yield d
+        return chunks()
 
     def alloc_root_table(self, capacity):
         import torch

@@ -66,7 +66,7 @@ int es_context_grid_timer(es_context* ctx, int enable);
 int es_context_grid_time(es_context* ctx, double* h_total_ms, int* h_launches);
 /* sizeof() of the ABI structs as this library was compiled, for binding self-checks:
  * which = 0 es_slab_analytic_params, 1 es_shoot_desc, 2 es_profiles, 3 es_root_table, 4 es_worker_spec,
- * 5 es_cyl_uniform_params; -1 for an unknown index. */
+ * 5 es_cyl_uniform_params, 6 es_complex_root_table, 7 es_field_profiles; -1 for an unknown index. */
 int es_abi_sizeof(int which);
 
 /* ========================================================================================================
@@ -523,6 +523,95 @@ int es_complex_eigenfunction(es_context* ctx, const es_problem* prob, int varian
                              int n_ext, double* d_ext_x,                   /* n x n_ext real     */
                              double* d_ext_value, double* d_ext_flux,      /* n x n_ext complex  */
                              uint8_t* d_status /* n, may be NULL */);
+
+/* ======================================================================================================
+ * (7) Perturbation fields of a cylinder mode, ready for VTK -- the third stage of the reference: its movie / vtk export
+ *     scripts turn the eigenfunction (P, xi_r) at a root into xi_phi, xi_z and the velocities and fill an
+ *     (r, theta, z, t) mesh in a four-deep Python loop
+ *       Cylinder/Non-uniform density/Coronal/Movies/Export_vtk.py            :764-818 amplitudes, :930-950 mesh
+ *       Cylinder/Non-uniform flow/Coronal/Movies/Gaussian_flow_export_vtk.py :796-852
+ *       Cylinder/Rotational flow/Photospheric/vtk export/v01_p1_kink_export_vtk.py :2179-2238
+ *     Cylinders only (the reference has no slab movies), radii POSITIVE as in those scripts.
+ *
+ *     es_cyl_polarisation: (P, xi_r) -> seven radial amplitudes.  One lane per (mode, radial point), nothing is marched.
+ *     The eigenfunction arrays are those es_shoot_eigenfunction writes (interior node 0 = boundary, exterior from the far
+ *     field to the boundary).  With
+ *       Om = w - m v_phi/r - k v_z        f = m B_phi/r + k B_z        g = m B_z/r + k B_phi
+ *       omega_A = m B_phi/r + k bA        omega_A^2, omega_c^2 = omega_A^2 qc   (the determinant's node entries, section 2)
+ *       T = f B_phi + rho v_phi Om        Q = -(Om^2 - omega_A^2) rho v_phi^2/r + 2 Om^2 B_phi^2/r + 2 Om B_phi v_phi f/r
+ *     interior:
+ *       xi_z   = [ f q (Om^2 P - Q xi_r)/(Om^2 rho (Om^2 - omega_c^2)) - (2 Om v_phi B_phi + f v_phi^2) xi_r/r
+ *                  - B_phi (g P - 2 B_z T xi_r/r)/(B_z rho (Om^2 - omega_A^2)) ] / (B_phi^2/B_z + B_z)
+ *       xi_phi = [ (g P - 2 B_z T xi_r/r)/(rho (Om^2 - omega_A^2)) + B_phi xi_z ] / B_z
+ *       v_r = -Om xi_r      v_phi = -Om xi_phi - s_phi r xi_r      v_z = -Om xi_z - s_z xi_r
+ *     exterior:
+ *       xi_phi = (m P/r)/(rho_e (w^2 - k^2 vA_e^2))     xi_z = k c_e^2 [w^2] P/(rho_e (w^2 - k^2 cT_e^2)(c_e^2 + vA_e^2))
+ *       v = -w xi
+ *     The interface is neutral about four oddities of the reference, which the caller chooses through the profile arrays
+ *     and the flags word:
+ *       1. q is the CONSTANT c_i0^2/(c_i0^2 + vA_i0^2) in the scripts, not the local ratio c^2/(c^2 + vA^2);
+ *       2. s_z is d(v_z/r)/dr there (Export_vtk.py:812-813), not dv_z/dr;
+ *       3. the exterior xi_z carries a factor w^2 the interior expression does not: ES_FIELD_REFERENCE switches it on;
+ *       4. the z-components get the angular factor -sin(m theta) (:940): ES_FIELD_Z_REFERENCE_ANGLE of the synthesis.
+ *     Output ordering is the reference's spatial = concatenate(ix[::-1], lx[::-1]): n_r = N + n_ext points per mode,
+ *     interior from the axis node out to the boundary, then exterior from the boundary out to the far field (the boundary
+ *     radius appears twice).  d_radius[i * n_r + j], d_amp[(i * 7 + c) * n_r + j], channels c in the order
+ *     xi_r, xi_phi, xi_z, P_T, v_r, v_phi, v_z (ES_AMP_*).
+ *     A mode whose eigenfunction rows are NaN (it was not ES_PT_OK) gets NaN in all its amplitudes; its radius row is
+ *     written and the other modes do not depend on it.  Nodes where Om^2 - omega_A^2 or Om^2 - omega_c^2 vanish give inf /
+ *     NaN at that node only: no guard, as in the reference.  n == 0 is a successful call that touches nothing; n_ext = 0
+ *     skips the exterior.  Asynchronous on the context's stream.
+ * ====================================================================================================== */
+/* Device arrays at the N interior nodes (node 0 = boundary), all required. */
+typedef struct es_field_profiles {
+  const double* r;                         /* node radii, > 0                                                       */
+  const double* rho; const double* Bz; const double* Bphi; const double* vz; const double* vphi;
+  const double* bA;                        /* omega_A = m B_phi/r + k bA       (B_z / sqrt(rho))                     */
+  const double* qc;                        /* omega_c^2 = omega_A^2 qc         (local c^2/(c^2 + vA^2))              */
+  const double* q;                         /* factor of the first term of xi_z (oddity 1)                           */
+  const double* s_phi;                     /* d(v_phi/r)/dr                                                         */
+  const double* s_z;                       /* dv_z/dr, or d(v_z/r)/dr (oddity 2)                                    */
+} es_field_profiles;
+
+enum { ES_AMP_XI_R = 0, ES_AMP_XI_PHI, ES_AMP_XI_Z, ES_AMP_P_T, ES_AMP_V_R, ES_AMP_V_PHI, ES_AMP_V_Z, ES_AMP_COUNT };
+enum { ES_FIELD_REFERENCE = 1,             /* es_cyl_polarisation: exterior xi_z with the factor w^2 (oddity 3)      */
+       ES_FIELD_Z_REFERENCE_ANGLE = 2,     /* es_cyl_field_synthesis: xi_z, v_z with -sin(m theta) (oddity 4)        */
+       ES_FIELD_BIG_ENDIAN = 4 };          /* es_cyl_field_synthesis: every float32 written is byte-swapped          */
+
+int es_cyl_polarisation(es_context* ctx, const double* d_k, const double* d_w, int n,
+                        int n_nodes, const double* d_int_value, const double* d_int_flux,           /* n x N      */
+                        int n_ext, const double* d_ext_x, const double* d_ext_value, const double* d_ext_flux,
+                        const es_field_profiles* profiles, int m, double rho_e, double vA_e, double c_e, double cT_e,
+                        int flags, double* d_radius /* n x n_r */, double* d_amp /* n x 7 x n_r */);
+
+/* es_cyl_field_synthesis: amplitudes of ONE mode -> frames on the (r, theta, z, t) mesh (Export_vtk.py:930-950), float32.
+ *   d_radius [n_r], d_amp [7 x n_r] as es_cyl_polarisation writes them for one mode; d_theta [n_theta], d_z [n_z],
+ *   d_t [n_t].  var_mask selects the variables by bit (ES_VAR_*; the first ten are the reference's varlist order), n_sel
+ *   of them, stored in ascending bit order.  With C = cos(k z - w t):
+ *     xi_r, P_T, v_r      A(r) cos(m theta) C
+ *     xi_phi, v_phi       A(r) (-sin(m theta)) C
+ *     xi_x = xi_r cos(theta) - xi_phi sin(theta),  xi_y = xi_r sin(theta) + xi_phi cos(theta);  v_x, v_y likewise
+ *     xi_z, v_z           A(r) cos(m theta) C (linear theory), or A(r) (-sin(m theta)) C with ES_FIELD_Z_REFERENCE_ANGLE
+ *   v_scale multiplies v_r, v_phi, v_z, v_x and v_y (the rotational script's reading; 1 = physical; the 25 and 400 of the
+ *   other scripts are plot scales).  The density perturbation of the scripts is not offered.
+ *   d_out [n_t][n_sel][n_z][n_theta][n_r] float32, the radial index fastest: VTK's point order, what
+ *   postprocess.write_vtk produces from arrays of shape (n_r, n_theta, n_z).
+ *   d_points [n_z][n_theta][n_r][3] = (r cos(theta), r sin(theta), z) float32; NULL skips it.
+ *   ES_FIELD_BIG_ENDIAN: every float32 written, points included, is byte-swapped: the buffer is the payload of a
+ *   legacy-VTK BINARY file as it stands.
+ *   Everything is computed in fp64 and rounded once to fp32.  d_out needs 4-byte alignment only: rows that start on a
+ *   16-byte boundary are written with 16-byte stores, the others with 4-byte stores.  Indices are size_t (the
+ *   reference's own mesh exceeds 2^31 bytes); n_z * n_theta * n_t and n_r must each be below 2^31.
+ *   n_t, n_z, n_theta or n_r == 0: nothing to write, ES_SUCCESS.  An empty or unknown mask is an argument error.
+ *   Asynchronous on the context's stream, no host read-back (the first call with larger theta / z / t tables grows the
+ *   context's scratch, which synchronises). */
+enum { ES_VAR_XI_R = 0, ES_VAR_XI_PHI, ES_VAR_P_T, ES_VAR_V_R, ES_VAR_V_PHI, ES_VAR_XI_X, ES_VAR_XI_Y, ES_VAR_V_X,
+       ES_VAR_V_Y, ES_VAR_V_Z, ES_VAR_XI_Z, ES_VAR_COUNT };
+int es_cyl_field_synthesis(es_context* ctx, const double* d_radius, const double* d_amp, int n_r,
+                           int m, double k, double w,
+                           const double* d_theta, int n_theta, const double* d_z, int n_z, const double* d_t, int n_t,
+                           uint32_t var_mask, double v_scale, int flags,
+                           float* d_points /* may be NULL */, float* d_out);
 
 #ifdef __cplusplus
 }
