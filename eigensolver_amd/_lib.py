@@ -32,6 +32,48 @@ class RefineStats(NamedTuple):
     evaluations: int    # determinant evaluations of the one-lane phase
 
 
+# es_shoot_audit_screening: status bit of a point the fp32 screening does not vouch for, kind bits of a flagged cell
+PT_SCREEN_UNSURE = 0x80
+AUDIT_MISSED, AUDIT_FALSE, AUDIT_STATUS, AUDIT_SIGN = 1, 2, 4, 8
+ERR_SCREENING = 7
+
+
+class ScreenAudit(NamedTuple):
+    """es_shoot_audit_screening read on the host (include/eigensolver_amd.h has the definitions).  Rows are indices into
+    the caller's full grid, also when only a sample of rows was audited."""
+    flagged: int        # cells with any kind bit (may exceed the table capacity)
+    missed: int         # fp64 brackets the merged grid does not have
+    false: int          # brackets of the merged grid that are not fp64 brackets
+    status: int         # vouched-for points whose status differs from the fp64 status
+    sign: int           # vouched-for points, both statuses OK, with the wrong sign
+    vouched_ok: int     # points vouched for with both statuses OK
+    unsure: int         # points sent back to fp64
+    brackets64: int     # fp64 brackets
+    min_margin: float   # least |D64| / |D_scr - D64| over the compared points (+inf: none)
+    min_margin_at: object   # its (row, col), or None
+    max_err: float      # largest fp32 error in units of max(|outer|, |inner|) (0: none)
+    max_err_at: object      # its (row, col), or None
+    row: object         # NumPy arrays: the first min(flagged, capacity) flagged cells in grid order ...
+    col: object
+    kind: object        # ... and their kind bits (AUDIT_*)
+
+    @property
+    def ok(self):
+        """The screening lost nothing: no missed or false bracket and no wrong status."""
+        return self.missed == 0 and self.false == 0 and self.status == 0
+
+
+def check_audit(report):
+    """Raise EsError, with the status string of ES_ERR_SCREENING and the first reported cell, unless report.ok."""
+    if report.ok:
+        return report
+    msg = load().es_status_string(ERR_SCREENING).decode()
+    first = (f"; first reported cell (row {int(report.row[0])}, col {int(report.col[0])}), kind {int(report.kind[0])}"
+             if len(report.row) else "")
+    raise EsError(f"libeigensolver_amd: {msg} (fp32 screening audit: {report.missed} missed and {report.false} false "
+                  f"bracket(s), {report.status} wrong status(es){first})")
+
+
 _lib = None
 
 
@@ -225,6 +267,7 @@ def _sig(lib):
     lib.es_shoot_find_roots_async.argtypes = [vp, vp, vp, i, vp, i, i, vp, vp, i, d, C.POINTER(RootTable), vp]
     lib.es_shoot_find_roots_screened_async.argtypes = [vp, vp, vp, i, vp, i, i, i, d, vp, vp, C.POINTER(RootTable), vp]
     lib.es_shoot_find_roots_mixed_async.argtypes = [vp, vp, vp, i, vp, i, i, i, d, vp, vp, C.POINTER(RootTable), vp]
+    lib.es_shoot_audit_screening.argtypes = [vp, i, i, vp, vp, vp, vp, vp, i, vp, vp, vp, vp]
     lib.es_root_table_pack.argtypes = [vp, C.POINTER(RootTable), i, d, vp, i, vp]
     lib.es_root_table_pack_async.argtypes = [vp, C.POINTER(RootTable), vp, d, vp, i, vp]
     lib.es_worker_run.argtypes = [vp, vp, C.POINTER(WorkerSpec), vp, i, vp, i, vp, vp, i, vp]

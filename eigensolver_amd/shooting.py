@@ -39,6 +39,39 @@ def read_screen_counts(counts, capacity):
     return r
 
 
+def audit_arrays(ctx, D_scr, st_scr, D64, st64, rel64=None, capacity=1024, rows=None):
+    """es_shoot_audit_screening on (nk, nw) CUDA tensors: the screened grid (float64 D_scr, uint8 st_scr) against the fp64
+    grid (D64, st64, optional rel64) -> _lib.ScreenAudit.  capacity bounds the table of flagged cells (0: counts only).
+    rows[i] is the row of the caller's full grid that row i of the arrays holds (None: the arrays are the full grid).
+    The call itself is asynchronous; reading the report is the host synchronisation."""
+    import torch
+    nk, nw = D64.shape
+    for t, dt in ((D_scr, torch.float64), (st_scr, torch.uint8), (D64, torch.float64), (st64, torch.uint8)):
+        assert t.is_cuda and t.dtype == dt and tuple(t.shape) == (nk, nw), "the four grids are (nk, nw) CUDA tensors"
+    assert rel64 is None or (rel64.is_cuda and rel64.dtype == torch.float64 and tuple(rel64.shape) == (nk, nw))
+    cap = int(capacity)
+    counts = torch.empty(10, dtype=torch.int64, device=D64.device)
+    worst = torch.empty(2, dtype=torch.float64, device=D64.device)
+    cell = torch.empty(cap, dtype=torch.int64, device=D64.device) if cap > 0 else None
+    kind = torch.empty(cap, dtype=torch.uint8, device=D64.device) if cap > 0 else None
+    D_scr, st_scr, D64, st64 = (t.contiguous() for t in (D_scr, st_scr, D64, st64))
+    rel64 = rel64.contiguous() if rel64 is not None else None
+    rc = ctx.lib.es_shoot_audit_screening(ctx.handle, nk, nw, _lib.ptr(D_scr), _lib.ptr(st_scr), _lib.ptr(D64),
+                                          _lib.ptr(st64), _lib.ptr(rel64) if rel64 is not None else None, cap,
+                                          _lib.ptr(cell) if cap > 0 else None, _lib.ptr(kind) if cap > 0 else None,
+                                          _lib.ptr(counts), _lib.ptr(worst))
+    _lib.check(ctx.handle, rc)
+    c = [int(x) for x in counts.tolist()]
+    wv = worst.tolist()
+    n = min(c[0], cap)
+    cells = cell[:n].cpu().numpy() if cap > 0 else np.zeros(0, dtype=np.int64)
+    kinds = kind[:n].cpu().numpy() if cap > 0 else np.zeros(0, dtype=np.uint8)
+    full_row = (lambda r: r) if rows is None else (lambda r: np.asarray(rows, dtype=np.int64)[r])
+    at = lambda x: None if x < 0 else (int(full_row(x // nw)), int(x % nw))     # noqa: E731
+    return _lib.ScreenAudit(*c[:8], float(wv[0]), at(c[8]), float(wv[1]), at(c[9]),
+                            full_row(cells // max(nw, 1)), cells % max(nw, 1), kinds)
+
+
 def var_mask(variables):
     """Mask of es_cyl_field_synthesis and the names in the order it stores them (ascending bit, _lib.VAR_NAMES)."""
     names = list(_lib.VAR_NAMES) if variables is None else list(variables)
@@ -393,6 +426,49 @@ class ShootProblem:
                 continue
             m = min(n.value, rt.capacity)
             return {key: v[:m] for key, v in t.items()}, n.value, D, st, tuple(stats)
+
+    def audit_screening(self, k, w, w_mode=W_PHASE_SPEED, rows=None, screened=None, capacity=1024):
+        """The fp32 screening of this grid against its fp64 evaluation, on the device (es_shoot_audit_screening): the check
+        that no fp64 bracket is missed, which find_roots_mixed itself cannot give.  Returns a _lib.ScreenAudit.
+        rows: the k-rows audited (rows are independent) -- None: all; an int s: rows 0, s, 2s, ...; an ascending index
+        array: those rows (with W_PER_ROW the same rows of w).  The audited rows are evaluated in fp64 (eval_grid) and,
+        with screened=None, screened with screen_grid; screened=(D, status) audits those rows of arrays the caller holds,
+        e.g. the merged output of find_roots_mixed.  Reported rows are indices into the full grid."""
+        import torch
+        dk, dw, nk, nw = self._grid_args(k, w, w_mode)
+        sel = None
+        if rows is not None:
+            if isinstance(rows, (int, np.integer)):
+                if rows < 1:
+                    raise ValueError("rows: a stride is at least 1")
+                sel = np.arange(0, nk, int(rows), dtype=np.int64)
+            else:
+                sel = np.asarray(rows, dtype=np.int64).reshape(-1)
+                if sel.size and (sel[0] < 0 or sel[-1] >= nk or np.any(np.diff(sel) <= 0)):
+                    raise ValueError("rows: ascending indices into the k-rows of the grid")
+            idx = torch.as_tensor(sel, device=dk.device)
+            dk = dk[idx]
+            if w_mode == W_PER_ROW:
+                dw = dw.reshape(nk, nw)[idx].contiguous()
+        D64, st64, rel64 = self.eval_grid(dk, dw, w_mode, want_rel=True)
+        if screened is None:
+            Ds, sts = self.screen_grid(dk, dw, w_mode)
+        else:
+            Ds, sts = (t.reshape(nk, nw) for t in screened)
+            if sel is not None:
+                Ds, sts = Ds[idx], sts[idx]
+        return audit_arrays(self.ctx, Ds, sts, D64, st64, rel64, capacity=capacity, rows=sel)
+
+    def find_roots_mixed_audited(self, k, w, w_mode=W_PHASE_SPEED, n_bisect=40, tol_percent=1e-3, capacity=None, table=None,
+                                 rows=None):
+        """find_roots_mixed, then audit_screening of its merged (D, status) on `rows`.  Returns find_roots_mixed's tuple
+        plus the ScreenAudit; raises EsError (the failure of ES_ERR_SCREENING) when the audit finds a missed or false
+        bracket or a wrong status."""
+        out = self.find_roots_mixed(k, w, w_mode=w_mode, n_bisect=n_bisect, tol_percent=tol_percent, capacity=capacity,
+                                    table=table)
+        report = self.audit_screening(k, w, w_mode=w_mode, rows=rows, screened=(out[2], out[3]))
+        _lib.check_audit(report)
+        return out + (report,)
 
     @staticmethod
     def _check_counts(counts):

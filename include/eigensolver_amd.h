@@ -230,7 +230,8 @@ int es_shoot_find_roots_async(es_context* ctx, const es_problem* prob, const dou
  * unnoticed; the thresholds are supported by measurement, not by an error bound (largest fp32 error among vouched-for points
  * 4.5e-3 of the scale over 3 800 random problems, tools/fuzz_mixed.py; every point of configs[4] in
  * tests/test_full_size_parity_gpu.py and tools/full_size_parity.py): in all of them the bracket set is identical and the root
- * table bit-identical to es_shoot_eval_grid + es_shoot_find_roots.
+ * table bit-identical to es_shoot_eval_grid + es_shoot_find_roots.  To check this half on your own equilibrium, run
+ * es_shoot_audit_screening (below) on the screened grid and the fp64 grid of the same points.
  *   1. the (k, omega) grid is marched in fp32 (exterior and boundary algebra in fp64); points at which fp32 cannot vouch
  *      for the sign of D or for the status (|D| < 5e-2 of max(|outer|, |inner|), a pole of D nearby, a coefficient within
  *      1e-3 of a singular point at some node, non-finite result) are marked and re-evaluated in fp64;
@@ -285,6 +286,48 @@ int es_shoot_find_roots_screened_async(es_context* ctx, const es_problem* prob, 
 int es_shoot_find_roots_mixed_async(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
                                     const double* d_w, int nw, int w_mode, int n_bisect, double tol_percent,
                                     double* d_D, uint8_t* d_status, es_root_table* table, int32_t* d_counts);
+
+/* Audit of the fp32 screening against the fp64 grid, on the device: the check of the EMPIRICAL half of the contract of
+ * es_shoot_find_roots_mixed (no fp64 bracket is missed), on the caller's own data.  A pure function of its arrays -- it
+ * needs no es_problem and marches nothing; it reads 26 bytes per cell (18 without d_rel64) once.
+ *   d_D_scr / d_status_scr: the screened grid, either what es_shoot_screen_grid wrote (unsure points carry the bit
+ *     ES_PT_SCREEN_UNSURE in their status) or what es_shoot_find_roots_screened / _mixed left behind (merged: no bit set, so
+ *     every point counts as vouched for).  d_D64 / d_status64 / d_rel64: es_shoot_eval_grid (flags = 0) of the same grid.
+ * Definitions, with cell c = row * nw + j:
+ *   unsure(c)  = status_scr[c] & ES_PT_SCREEN_UNSURE;  vouched(c) = !unsure(c).
+ *   merged grid: Dm = unsure ? D64 : D_scr, stm = unsure ? status64 : status_scr -- what the search brackets on (its fp64
+ *     re-evaluation of an unsure point gives the value of es_shoot_eval_grid bit for bit).
+ *   B(D, st)(c) = j < nw - 1 && st[c] == ES_PT_OK && st[c + 1] == ES_PT_OK && D[c] * D[c + 1] < 0: the bracket predicate of
+ *     es_shoot_find_roots (NaN products compare false, the last column is never a bracket, a bracket never spans a row).
+ *   kind bits of a cell:  ES_AUDIT_MISSED  B(D64, st64) && !B(Dm, stm)          ES_AUDIT_FALSE  B(Dm, stm) && !B(D64, st64)
+ *                         ES_AUDIT_STATUS  vouched && stm != status64
+ *                         ES_AUDIT_SIGN    vouched, both statuses ES_PT_OK, signbit(D_scr) != signbit(D64)
+ *   compared points: vouched, both statuses ES_PT_OK, D_scr != D64, neither NaN.  Over them
+ *     sign margin = fabs(D64) / fabs(D_scr - D64): the factor by which the fp32 error at the point would have to grow to
+ *       flip the sign (scale-free; below 1 the sign is wrong);
+ *     err = fabs(D_scr - D64) / (fabs(D64) * 100.0 / rel64), where d_rel64 is given, D64 != 0 and rel64 is finite and
+ *       positive: the fp32 error in units of max(|outer|, |inner|), the scale the screening threshold 5e-2 is measured in.
+ *     A statistic that is itself NaN (inf / inf) is skipped.
+ * d_counts (10 words): [0] flagged cells (any kind bit; may exceed capacity), [1] missed, [2] false, [3] status, [4] sign,
+ *   [5] points vouched for with both statuses ES_PT_OK, [6] unsure points, [7] fp64 brackets, [8] cell of the minimum
+ *   margin (-1: no compared point), [9] cell of the maximum err (-1: none, or d_rel64 == NULL).
+ * d_worst (2 doubles): [0] minimum margin (+inf if none), [1] maximum err (0 if none).  Ties go to the smallest cell; counts
+ *   are integer sums and the extrema are compared, never accumulated, so the result is reproducible bit for bit.
+ * Table: the first min([0], capacity) flagged cells in ascending cell order, d_cell[pos] = c, d_kind[pos] = its kind bits;
+ *   entries beyond that are left alone.
+ * Asynchronous on the context's stream, nothing is read back; a call that grows the context's scratch (the first one at a
+ * larger grid) frees and allocates device memory, which synchronises.  nk * nw == 0: counts 0, cells -1, worst (+inf, 0),
+ * ES_SUCCESS (the four grid pointers may then be NULL).  ES_ERR_INVALID_ARG, with nothing enqueued: a null context, nk, nw
+ * or capacity negative, nk * nw >= 2^31, a required pointer null, d_cell or d_kind null with capacity > 0. */
+enum { ES_PT_SCREEN_UNSURE = 0x80 };   /* status bit es_shoot_screen_grid leaves on points fp32 does not vouch for */
+enum { ES_AUDIT_MISSED = 1, ES_AUDIT_FALSE = 2, ES_AUDIT_STATUS = 4, ES_AUDIT_SIGN = 8 };   /* kind bits of a cell */
+
+int es_shoot_audit_screening(es_context* ctx, int nk, int nw,
+        const double* d_D_scr, const uint8_t* d_status_scr,      /* nk x nw: the screened grid                 */
+        const double* d_D64,  const uint8_t* d_status64,         /* nk x nw: es_shoot_eval_grid, flags = 0      */
+        const double* d_rel64 /* may be NULL */,
+        int capacity, int64_t* d_cell, uint8_t* d_kind,          /* `capacity` entries each; NULL iff capacity == 0 */
+        int64_t* d_counts /* 10 words */, double* d_worst /* 2 doubles */);
 
 /* Refinement rule of the context, read by all six searches above at their refinement step (signatures unchanged).
  *   ES_REFINE_SECTION (default): the rule described at es_shoot_find_roots, R = ceil(n_bisect ln 2 / ln 17) rounds of
