@@ -228,6 +228,9 @@ class FieldProfiles(C.Structure):
 AMP_NAMES = ("xi_r", "xi_phi", "xi_z", "P_T", "v_r", "v_phi", "v_z")                       # ES_AMP_*
 VAR_NAMES = ("xi_r", "xi_phi", "P_T", "v_r", "v_phi", "xi_x", "xi_y", "v_x", "v_y", "v_z", "xi_z")   # ES_VAR_* (mask bits)
 FIELD_REFERENCE, FIELD_Z_REFERENCE_ANGLE, FIELD_BIG_ENDIAN = 1, 2, 4
+# ---- Cartesian sampling and vorticity (section 8) ----------------------------------------------------------------
+VORT_NAMES = ("Wr_C", "Wr_S", "Wphi_C", "Wphi_S", "Wz_C")                                     # ES_VORT_*
+CVAR_NAMES = ("P_T", "xi_x", "xi_y", "xi_z", "v_x", "v_y", "v_z", "vort_x", "vort_y", "vort_z")   # ES_CVAR_* (mask bits)
 
 
 def _sig(lib):
@@ -288,4 +291,9 @@ def _sig(lib):
     lib.es_cyl_polarisation.argtypes = [vp, vp, vp, i, i, vp, vp, i, vp, vp, vp, C.POINTER(FieldProfiles), i, d, d, d, d,
                                         i, vp, vp]
     lib.es_cyl_field_synthesis.argtypes = [vp, vp, vp, i, i, d, d, vp, i, vp, i, vp, i, C.c_uint32, d, i, vp, vp]
+    # (8) Cartesian sampling and vorticity
+    lib.es_cyl_vorticity_amplitudes.argtypes = [vp, vp, vp, i, i, i, i, vp, vp]
+    lib.es_cyl_cartesian_synthesis.argtypes = [vp, vp, vp, vp, i, i, i, d, d, vp, i, vp, i, vp, i, vp, i, C.c_uint32, d,
+                                               C.c_float, i, vp]
+    lib.es_cyl_cartesian_split.argtypes = [i, i, i, i] + [C.POINTER(i)] * 5
     return lib

@@ -164,3 +164,52 @@ def write_vtk_frames(prefix, fields_iter, names=None):
                                           [host[v][i] for v in use], use))
             frame += 1
     return files
+
+
+def write_vtk_rectilinear(dump_file, x, y, z, variables_be, names):
+    """Legacy-VTK RECTILINEAR_GRID, BINARY, of scalar fields on the Cartesian mesh x [n_x], y [n_y], z [n_z] (host arrays,
+    written as big-endian float32 `X_COORDINATES n float` etc.).  Every entry of variables_be is an already-packed
+    payload of n_x*n_y*n_z big-endian float32 values, x fastest -- one frame of one variable of
+    ShootProblem.cartesian_fields(..., big_endian=True), copied to the host.  Writes `<dump_file>.vtk`."""
+    x, y, z = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y, z))
+    if len(variables_be) != len(names):
+        raise ValueError("one name per variable")
+    n = x.size * y.size * z.size
+    with open(str(dump_file) + ".vtk", "wb") as f:
+        f.write(b"# vtk DataFile Version 3.0\n")
+        f.write(b"vtk output\n")
+        f.write(b"BINARY\n")
+        f.write(b"DATASET RECTILINEAR_GRID\n")
+        f.write(("DIMENSIONS %d %d %d\n" % (x.size, y.size, z.size)).encode())
+        for axis, a in (("X", x), ("Y", y), ("Z", z)):
+            f.write(("%s_COORDINATES %d float\n" % (axis, a.size)).encode())
+            f.write(a.astype(">f4").tobytes())
+            f.write(b"\n")
+        f.write(("POINT_DATA %d\n" % n).encode())
+        for name, var in zip(names, variables_be):
+            buf = _payload(var)
+            if len(buf) != 4 * n:
+                raise ValueError(f"variable {name!r} has {len(buf)} bytes, the grid needs {4 * n}")
+            f.write(("SCALARS %s float\n" % name).encode())
+            f.write(b"LOOKUP_TABLE default\n")
+            f.write(buf)
+            f.write(b"\n")
+    return str(dump_file) + ".vtk"
+
+
+def write_vtk_rectilinear_frames(prefix, x, y, z, fields_iter, names=None):
+    """One RECTILINEAR_GRID file per frame from ShootProblem.cartesian_fields(..., big_endian=True): `<prefix><t>.vtk`
+    with t the frame number counted over all chunks, as write_vtk_frames names them.  fields_iter is the dict
+    `cartesian_fields` returns or the generator it returns with frames_per_call; x, y, z are the host arrays the mesh was
+    built from; names defaults to the variables of the chunks.  Each chunk is copied to the host once.  Returns the list
+    of files written."""
+    if isinstance(fields_iter, dict):
+        fields_iter = [fields_iter]
+    files, frame = [], 0
+    for chunk in fields_iter:
+        use = list(chunk["names"]) if names is None else list(names)
+        host = {v: chunk[v].cpu() for v in use}
+        for i in range(chunk["frames"].shape[0]):
+            files.append(write_vtk_rectilinear(str(prefix) + str(frame), x, y, z, [host[v][i] for v in use], use))
+            frame += 1
+    return files

@@ -128,6 +128,74 @@ def field_synthesis(ctx, radius, amp, m, k, w, theta, z, t, variables=None, v_sc
     return out, pts, names
 
 
+def cartesian_var_mask(variables):
+    """Mask of es_cyl_cartesian_synthesis and the names in the order it stores them (ascending bit, _lib.CVAR_NAMES)."""
+    names = list(_lib.CVAR_NAMES) if variables is None else list(variables)
+    unknown = [v for v in names if v not in _lib.CVAR_NAMES]
+    if unknown:
+        raise ValueError(f"unknown Cartesian field variable(s) {unknown}: choose from {_lib.CVAR_NAMES}")
+    mask = 0
+    for v in names:
+        mask |= 1 << _lib.CVAR_NAMES.index(v)
+    return mask, [v for b, v in enumerate(_lib.CVAR_NAMES) if (mask >> b) & 1]
+
+
+def vorticity_amplitudes(ctx, radius, amp, n_nodes, n_ext, m, k):
+    """es_cyl_vorticity_amplitudes on the tables of es_cyl_polarisation (radius [n, n_r], amp [n, 7, n_r], k [n], CUDA
+    float64, n_r = n_nodes + n_ext): the five radial amplitudes of curl v, vort [n, 5, n_r] in the order _lib.VORT_NAMES.
+    Enqueued on the context's stream."""
+    import torch
+    n, n_r = radius.shape
+    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (n, 7, n_r) and k.shape == (n,)
+    for a in (radius, amp, k):
+        assert a.is_cuda and a.dtype == torch.float64 and a.is_contiguous()
+    vort = torch.empty((n, 5, n_r), dtype=torch.float64, device=radius.device)
+    rc = ctx.lib.es_cyl_vorticity_amplitudes(ctx.handle, _lib.ptr(radius), _lib.ptr(amp), n, int(n_nodes), int(n_ext),
+                                             int(m), _lib.ptr(k), _lib.ptr(vort))
+    _lib.check(ctx.handle, rc)
+    return vort
+
+
+def cartesian_synthesis(ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z, t, variables=None, v_scale=1.0,
+                        fill=float("nan"), flags=0, out=None):
+    """es_cyl_cartesian_synthesis for the tables of one mode (radius [n_r], amp [7, n_r], vort [5, n_r] or None, CUDA
+    float64): float32 frames out[n_t, n_sel, n_z, n_y, n_x] in the order of cartesian_var_mask(variables)[1].  x, y, z,
+    t: CUDA float64 vectors.  `out`: a preallocated contiguous float32 tensor of that shape (4-byte alignment suffices).
+    Enqueued on the context's stream; returns (out, names)."""
+    import torch
+    mask, names = cartesian_var_mask(variables)
+    n_r = radius.numel()
+    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (7, n_r) and (vort is None or vort.shape == (5, n_r))
+    for a in (radius, amp, vort, x, y, z, t):
+        assert a is None or (a.is_cuda and a.dtype == torch.float64 and a.is_contiguous())
+    shape = (t.numel(), len(names), z.numel(), y.numel(), x.numel())
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=radius.device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous()
+    rc = ctx.lib.es_cyl_cartesian_synthesis(ctx.handle, _lib.ptr(radius), _lib.ptr(amp),
+                                            _lib.ptr(vort) if vort is not None else None, int(n_nodes), int(n_ext),
+                                            int(m), float(k), float(w), _lib.ptr(x), x.numel(), _lib.ptr(y), y.numel(),
+                                            _lib.ptr(z), z.numel(), _lib.ptr(t), t.numel(), mask, float(v_scale),
+                                            float(fill), int(flags), _lib.ptr(out))
+    _lib.check(ctx.handle, rc)
+    return out, names
+
+
+def _require_exterior_points(n_ext):
+    if int(n_ext) != 0 and int(n_ext) < 3:
+        raise ValueError(f"n_ext = {n_ext}: the exterior needs at least 3 points (radial derivative and interpolation "
+                         "per region), or 0 to leave it out")
+
+
+def cartesian_split(ctx, n_x, n_y, n_z, n_t):
+    """The launch shape of es_cyl_cartesian_synthesis for a mesh (es_cyl_cartesian_split): dict of pieces, z_chunk, z_parts,
+    items_per_group, groups."""
+    v = [C.c_int(0) for _ in range(5)]
+    rc = ctx.lib.es_cyl_cartesian_split(int(n_x), int(n_y), int(n_z), int(n_t), *[C.byref(a) for a in v])
+    _lib.check(ctx.handle, rc)
+    return dict(zip(("pieces", "z_chunk", "z_parts", "items_per_group", "groups"), (a.value for a in v)))
+
+
 def make_desc(eq, mode, m=None):
     """es_shoot_desc + profile dict for equilibrium `eq` and mode "kink" / "sausage" (azimuthal order m for
     cylinders defaults to the reference's 1 / 0)."""
@@ -337,6 +405,59 @@ class ShootProblem:
                 points = d["points"]
                 yield d
         return chunks()
+
+    def vorticity_amplitudes(self, k, w, n_ext=500, reference_quirks=False):
+        """`polarisation` followed by es_cyl_vorticity_amplitudes: dict of CUDA tensors radius [n, n_r], amp [n, 7, n_r] and
+        vort [n, 5, n_r] (channels _lib.VORT_NAMES), the radial amplitudes of curl v in the linear-theory convention;
+        radial derivatives per region, never across the interface.  reference_quirks selects the polarisation's profile
+        quirks 1 - 3 only.  The exterior, when present, needs n_ext >= 3."""
+        self._require_positive_cylinder()
+        _require_exterior_points(n_ext)
+        pol = self.polarisation(k, w, n_ext=n_ext, reference_quirks=reference_quirks)
+        dk = self._dev(k).reshape(-1)
+        pol["vort"] = vorticity_amplitudes(self.ctx, pol["radius"], pol["amp"], int(self.desc.n_nodes), int(n_ext),
+                                           int(self.desc.m), dk)
+        return pol
+
+    def cartesian_fields(self, k, w, x, y, z, t, variables=None, v_scale=1.0, fill=float("nan"), big_endian=False,
+                         frames_per_call=None, n_ext=500, reference_quirks=False):
+        """Fields of ONE root (k, omega) on the Cartesian mesh (x, y, z, t), the vorticity of the velocity included:
+        float32 CUDA tensors in the point order of a legacy-VTK RECTILINEAR_GRID (x fastest).  Returns a dict
+            x [n_x], y [n_y], z [n_z], t [n_t], names, frames [n_t, n_sel, n_z, n_y, n_x], <name>: frames[:, i]
+        `variables` defaults to all of _lib.CVAR_NAMES and is stored in that order.  Points outside the tabulated radii
+        (the hole inside the axis node, beyond the far field of n_ext points, r = 0) carry `fill`.
+        frames_per_call: a generator of such dicts, at most that many frames each.  reference_quirks selects only the
+        polarisation's profile quirks 1 - 3; the angular factor of the z-components is always linear theory's cos(m theta).
+        v_scale multiplies the velocities and the vorticity.  big_endian: every float32 is byte-swapped on the device,
+        ready for postprocess.write_vtk_rectilinear_frames."""
+        self._require_positive_cylinder()
+        if np.ndim(k) != 0 or np.ndim(w) != 0:
+            raise ValueError("cartesian_fields() takes one root: scalar k and omega")
+        _require_exterior_points(n_ext)
+        mask, names = cartesian_var_mask(variables)
+        want_vort = any(v.startswith("vort_") for v in names)
+        if want_vort:
+            tab = self.vorticity_amplitudes([float(k)], [float(w)], n_ext=n_ext, reference_quirks=reference_quirks)
+        else:
+            tab = self.polarisation([float(k)], [float(w)], n_ext=n_ext, reference_quirks=reference_quirks)
+        radius, amp = tab["radius"][0], tab["amp"][0]
+        vort = tab["vort"][0] if want_vort else None
+        dx, dy, dz, dt = (self._dev(a).reshape(-1) for a in (x, y, z, t))
+        flags = _lib.FIELD_BIG_ENDIAN if big_endian else 0
+
+        def chunk(t_part):
+            out, _ = cartesian_synthesis(self.ctx, radius, amp, vort, int(self.desc.n_nodes), int(n_ext), int(self.desc.m),
+                                         k, w, dx, dy, dz, t_part, names, v_scale, fill, flags)
+            d = dict(x=dx, y=dy, z=dz, t=t_part, names=names, frames=out)
+            d.update({v: out[:, i] for i, v in enumerate(names)})
+            return d
+
+        if frames_per_call is None:
+            return chunk(dt)
+        step = int(frames_per_call)
+        if step < 1:
+            raise ValueError("frames_per_call must be >= 1")
+        return (chunk(dt[a:a + step]) for a in range(0, dt.numel(), step))
 
     def alloc_root_table(self, capacity):
         import torch

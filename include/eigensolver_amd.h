@@ -656,6 +656,86 @@ int es_cyl_field_synthesis(es_context* ctx, const double* d_radius, const double
                            uint32_t var_mask, double v_scale, int flags,
                            float* d_points /* may be NULL */, float* d_out);
 
+/* ======================================================================================================
+ * (8) Cartesian sampling of a cylinder mode, with its vorticity -- the fourth stage of the reference: its movie and
+ *     2-D visualisation scripts flatten the polar mesh of stage three, resample it onto a Cartesian one with
+ *     scipy.interpolate.griddata and difference the result with np.gradient
+ *       Cylinder/Non-uniform flow/Coronal/Movies/Vorticity_gaussian_flow.py :1190-1262   (and 23 more scripts)
+ *     Here r and the angle factors are computed at the Cartesian point itself, only the radial amplitudes are
+ *     interpolated, separately on each side of the interface, and curl v is a closed expression.
+ *     Two things of the scripts are NOT offered: np.gradient along the (r, theta, z) index axes with unit spacing read as
+ *     d/dx, d/dy, d/dz (:1227-1233), and a triangulation across r = boundary, where v_phi and v_z jump.
+ *
+ *     Convention: the synthesis's linear-theory one (section 7 without ES_FIELD_Z_REFERENCE_ANGLE), C = cos(k z - w t),
+ *     S = sin(k z - w t):
+ *       v_r = a_r cos(m theta) C        v_phi = a_phi (-sin(m theta)) C        v_z = a_z cos(m theta) C
+ *     with a_r, a_phi, a_z the channels ES_AMP_V_R, ES_AMP_V_PHI, ES_AMP_V_Z.  curl v in cylindrical components:
+ *       w_r   = sin(m theta) (Wr_C C + Wr_S S)      Wr_C   = -m a_z / r                 Wr_S   = -k a_phi
+ *       w_phi = cos(m theta) (Wphi_C C + Wphi_S S)  Wphi_C = -a_z'                      Wphi_S = -k a_r
+ *       w_z   = sin(m theta) Wz_C C                 Wz_C   = (m a_r - a_phi - r a_phi') / r
+ *     The -sin(m theta) reading of the z-components (ES_FIELD_Z_REFERENCE_ANGLE) has another curl and is not offered:
+ *     the flag is an argument error in this section.
+ *
+ *     es_cyl_vorticity_amplitudes: d_radius [n x n_r], d_amp [n x 7 x n_r] exactly as es_cyl_polarisation writes them,
+ *     n_r = n_nodes + n_ext (interior from the axis node out to the boundary, then exterior from the boundary outwards,
+ *     the boundary radius twice), d_k [n]  ->  d_vort [(i * 5 + c) * n_r + j], channels c = ES_VORT_*.
+ *     One lane per (mode, radial point).  The radial derivatives are DEFINED as np.gradient(a, r, edge_order=2) of each
+ *     region on its own, indices [0, n_nodes) and [n_nodes, n_r): with hs, hd the spacings below and above a node,
+ *       inside a region   (hs^2 f+ + (hd^2 - hs^2) f0 - hd^2 f-) / (hs hd (hs + hd))
+ *       at a region end   the second-order one-sided three-point formula,
+ *     both for non-uniform radii.  Nothing is differenced across the interface: the tangential velocity jumps there and
+ *     the vortex sheet is not a field value.  A region that is present needs >= 3 points (argument error otherwise);
+ *     n_nodes = 0 or n_ext = 0 leaves that region out.  NaN / inf amplitudes reach the nodes whose stencil touches them
+ *     and no others.  n == 0 is a successful call that touches nothing.  Asynchronous on the context's stream.
+ * ====================================================================================================== */
+enum { ES_VORT_R_C = 0, ES_VORT_R_S, ES_VORT_PHI_C, ES_VORT_PHI_S, ES_VORT_Z_C, ES_VORT_COUNT };
+
+int es_cyl_vorticity_amplitudes(es_context* ctx, const double* d_radius /* n x n_r */,
+                                const double* d_amp /* n x 7 x n_r */, int n, int n_nodes, int n_ext, int m,
+                                const double* d_k /* n */, double* d_vort /* n x 5 x n_r */);
+
+/* es_cyl_cartesian_synthesis: amplitudes of ONE mode -> frames on the (x, y, z, t) mesh, float32.
+ *   d_radius [n_r], d_amp [7 x n_r], d_vort [5 x n_r] of one mode (d_vort may be NULL if no vorticity bit is set);
+ *   d_x [n_x], d_y [n_y], d_z [n_z], d_t [n_t].  var_mask selects by bit (ES_CVAR_*), n_sel variables stored in ascending
+ *   bit order.  At a mesh point r = hypot(x, y), (cos theta, sin theta) = (x / r, y / r), cos(m theta) and sin(m theta)
+ *   from those two by angle addition.  With A(r) the interpolated amplitude:
+ *     P_T, xi_z, v_z      A cos(m theta) C
+ *     xi_x = xi_r cos(theta) - xi_phi sin(theta),  xi_y = xi_r sin(theta) + xi_phi cos(theta)   with
+ *                         xi_r = A cos(m theta) C, xi_phi = A (-sin(m theta)) C as in section 7;  v_x, v_y likewise
+ *     vort_x = w_r cos(theta) - w_phi sin(theta),  vort_y = w_r sin(theta) + w_phi cos(theta),  vort_z = w_z
+ *   v_scale multiplies the velocities and the vorticity.
+ *   Region, decided by the tabulated radii:
+ *     radius[0] <= r <= radius[n_nodes-1]            interior (a point exactly on the boundary radius is interior)
+ *     radius[n_nodes-1] < r <= radius[n_r-1]         exterior
+ *     anything else -- the hole inside the axis node, beyond the far field, r = 0, NaN coordinates -- gets `fill` in every
+ *     selected variable, as bits (a NaN keeps its payload), byte-swapped if requested.
+ *   Inside a region the bracketing nodes of the ascending radii are found by bisection (no spacing is assumed) and every
+ *   amplitude is A_j + (A_j+1 - A_j) (r - r_j) / (r_j+1 - r_j); exactly on the last node of a region that node's value.
+ *   A region that is present needs >= 3 points; at least one must be present.
+ *   d_out [n_t][n_sel][n_z][n_y][n_x] float32, x fastest: the point order of a legacy-VTK RECTILINEAR_GRID.
+ *   flags: ES_FIELD_BIG_ENDIAN only.  Everything is computed in fp64 and rounded once.  d_out needs 4-byte alignment only:
+ *   the (y, x) points of a z plane are contiguous and are written with 16-byte stores when every plane starts on a
+ *   16-byte boundary (n_x n_y a multiple of 4, d_out 16-byte aligned), with 4-byte stores otherwise, the same bits either
+ *   way.  Indices are size_t; n_z * n_t must be below 2^31.
+ *   n_x, n_y, n_z or n_t == 0: nothing to write, ES_SUCCESS.  An empty or unknown mask, a vorticity bit without d_vort
+ *   and a misaligned d_out are argument errors.  Asynchronous on the context's stream, no host read-back (the first call
+ *   with larger z / t tables grows the context's scratch, which synchronises). */
+enum { ES_CVAR_P_T = 0, ES_CVAR_XI_X, ES_CVAR_XI_Y, ES_CVAR_XI_Z, ES_CVAR_V_X, ES_CVAR_V_Y, ES_CVAR_V_Z, ES_CVAR_VORT_X,
+       ES_CVAR_VORT_Y, ES_CVAR_VORT_Z, ES_CVAR_COUNT };
+int es_cyl_cartesian_synthesis(es_context* ctx, const double* d_radius, const double* d_amp /* 7 x n_r */,
+                               const double* d_vort /* 5 x n_r, may be NULL if no vorticity bit is set */,
+                               int n_nodes, int n_ext, int m, double k, double w,
+                               const double* d_x, int n_x, const double* d_y, int n_y, const double* d_z, int n_z,
+                               const double* d_t, int n_t, uint32_t var_mask, double v_scale, float fill, int flags,
+                               float* d_out);
+
+/* The launch shape es_cyl_cartesian_synthesis uses for a mesh (no device work; for tools and tests, as es_shoot_grid_shape):
+ * a z plane is cut into `pieces` of 256 points; a frame's n_z planes into z_parts pieces of z_chunk planes (the last one
+ * shorter when z_chunk does not divide n_z); the n_t * z_parts (frame, z piece) items go to `groups` workgroups per piece,
+ * items_per_group each (the last group shorter when it does not divide them).  All sizes must be positive. */
+int es_cyl_cartesian_split(int n_x, int n_y, int n_z, int n_t, int* pieces, int* z_chunk, int* z_parts,
+                           int* items_per_group, int* groups);
+
 #ifdef __cplusplus
 }
 #endif

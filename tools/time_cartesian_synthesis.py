@@ -1,0 +1,156 @@
+"""GPU timing aid: the Cartesian sampling of a cylinder mode with its vorticity (es_cyl_cartesian_synthesis) against what
+a user would write without it and against the store bandwidth of the device, on one device.
+
+Mesh: the reference's 267 x 267 Cartesian slice (x, y in [-2, 2]) x 31 heights, all ten variables, chunks of 8 frames:
+8 x 10 x 31 x 267 x 267 float32 = 707 MB per call.  The tables are those of ShootProblem.vorticity_amplitudes at one
+(k, omega) of the coronal density cylinder (width 0.9), 500 interior nodes + 700 exterior points.  Three legs, all writing
+the same number of bytes into the same buffer, each between two device events on the context's stream, alternating repeat
+by repeat in one process so that drift hits all alike:
+
+    kernel   es_cyl_cartesian_synthesis (its (z, t) table pre-pass included)
+    torch    the same fields as a torch expression in fp64 (hypot / searchsorted / lerp / broadcast), cast to fp32 and
+             copied into the buffer
+    fill     Tensor.fill_ of the buffer: the store-bandwidth yardstick of this device on this day
+
+Per leg one JSON line: median / min / max ms over the repeats and GB/s of the median; then the ratios kernel / fill and
+torch / kernel, and the time of one es_cyl_vorticity_amplitudes call (one mode, 1 200 radial points).
+
+    python tools/time_cartesian_synthesis.py [--repeats 20] [--warmup 3] [--frames 8] [--nxy 267] [--calls 1] [--out profiles/cartesian_synthesis_timing.jsonl]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def torch_fields(torch, radius, amp, vort, N, m, k, w, x, y, z, t, v_scale, fill, out):
+    """Section 8 as broadcast torch expressions, fp64, cast to fp32: region by comparison, bracket by searchsorted per
+    region, linear interpolation, the angle factors from atan2."""
+    n_r = radius.numel()
+    X, Y = x[None, :], y[:, None]
+    r = torch.hypot(X, Y)
+    inside = (r >= radius[0]) & (r <= radius[N - 1])
+    outside = (r > radius[N - 1]) & (r <= radius[n_r - 1])
+    valid = (inside | outside) & (r > 0)
+    ji = (torch.searchsorted(radius[:N].contiguous(), r, right=True) - 1).clamp(0, N - 2)
+    je = N + (torch.searchsorted(radius[N:].contiguous(), r, right=True) - 1).clamp(0, n_r - N - 2)
+    j = torch.where(inside, ji, je)
+    r0, r1 = radius[j], radius[j + 1]
+    frac = (r - r0) / (r1 - r0)
+    last = r >= r1
+    lerp = lambda a: torch.where(last, a[j + 1], a[j] + (a[j + 1] - a[j]) * frac)      # noqa: E731
+    A = {n: lerp(a) for n, a in zip(("xi_r", "xi_phi", "xi_z", "P_T", "v_r", "v_phi", "v_z"), amp)}
+    V = {n: lerp(a) for n, a in zip(("Wr_C", "Wr_S", "Wphi_C", "Wphi_S", "Wz_C"), vort)}
+    th = torch.atan2(Y.expand_as(r), X.expand_as(r))
+    ct, st, cm, sm = X / r, Y / r, torch.cos(m * th), torch.sin(m * th)
+    vs = v_scale
+    wr_c, wr_s, wp_c, wp_s = sm * V["Wr_C"], sm * V["Wr_S"], cm * V["Wphi_C"], cm * V["Wphi_S"]
+    zero = None
+    coef = [(A["P_T"] * cm, zero),
+            (A["xi_r"] * cm * ct + A["xi_phi"] * sm * st, zero), (A["xi_r"] * cm * st - A["xi_phi"] * sm * ct, zero),
+            (A["xi_z"] * cm, zero),
+            (vs * (A["v_r"] * cm * ct + A["v_phi"] * sm * st), zero), (vs * (A["v_r"] * cm * st - A["v_phi"] * sm * ct), zero),
+            (vs * A["v_z"] * cm, zero),
+            (vs * (wr_c * ct - wp_c * st), vs * (wr_s * ct - wp_s * st)),
+            (vs * (wr_c * st + wp_c * ct), vs * (wr_s * st + wp_s * ct)),
+            (vs * sm * V["Wz_C"], zero)]
+    ph = k * z[None, :, None, None] - w * t[:, None, None, None]
+    C, S = torch.cos(ph), torch.sin(ph)
+    fill_t = torch.tensor(fill, dtype=torch.float64, device=r.device)
+    for i, (c, s) in enumerate(coef):
+        f = c[None, None] * C
+        if s is not None:
+            f = f + s[None, None] * S
+        out[:, i] = torch.where(valid[None, None], f, fill_t).to(torch.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--nxy", type=int, default=267, help="points along x and along y (267: the reference's slice)")
+    ap.add_argument("--calls", type=int, default=1, help="calls per timed window (times are per call); above 1 the host's "
+                    "launch latency hides behind the previous call")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    a = ap.parse_args()
+    assert a.repeats >= 10, "at least 10 timed repeats per leg"
+    import numpy as np
+    import torch
+    from eigensolver_amd import ShootProblem, _lib, equilibrium as q, shooting
+    assert torch.cuda.is_available(), "this tool measures on the GPU; there is nothing to fall back to"
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.Stream(device=dev)
+    ctx = _lib.Context(dev.index or 0, stream=stream)
+    k, w, v_scale, fill = 1.2, 3.741567685037965, 25.0, 0.0
+    N, n_ext, n_xy, n_z = 500, 700, a.nxy, 31
+    with torch.cuda.stream(stream):
+        gp = ShootProblem(q.CylinderDensity(width=0.9, r_sign=1.0, n_nodes=N, ic=(1e-8, 1e-8)), "kink", ctx=ctx)
+        tab = gp.vorticity_amplitudes([k], [w], n_ext=n_ext)
+        radius, amp, vort = (tab[n][0].contiguous() for n in ("radius", "amp", "vort"))
+        assert bool(torch.isfinite(amp).all()) and bool(torch.isfinite(vort).all()), "the mode is not ES_PT_OK"
+        T = lambda v: torch.as_tensor(v, dtype=torch.float64, device=dev)    # noqa: E731
+        x, y, z = T(np.linspace(-2.0, 2.0, n_xy)), T(np.linspace(-2.0, 2.0, n_xy)), T(np.linspace(0.01, 5.0, n_z))
+        t = T(np.linspace(0.01, 2.0 * np.pi, 80)[:a.frames])
+        m = int(gp.desc.m)
+        out = torch.empty((a.frames, 10, n_z, n_xy, n_xy), dtype=torch.float32, device=dev)
+        kk = T([k])
+    nbytes = out.numel() * 4
+    legs = {
+        "kernel": lambda: shooting.cartesian_synthesis(ctx, radius, amp, vort, N, n_ext, m, k, w, x, y, z, t, None, v_scale,
+                                                       fill, 0, out=out),
+        "torch": lambda: torch_fields(torch, radius, amp, vort, N, float(m), k, w, x, y, z, t, v_scale, fill, out),
+        "fill": lambda: out.fill_(1.0),
+        "vorticity_amplitudes": lambda: shooting.vorticity_amplitudes(ctx, tab["radius"], tab["amp"], N, n_ext, m, kk),
+    }
+    ms = {name: [] for name in legs}
+    check = {}
+    for it in range(a.warmup + a.repeats):
+        for name, run in legs.items():
+            with torch.cuda.stream(stream):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.calls):
+                    run()
+                e1.record(stream)
+                if it == 0 and name in ("kernel", "torch"):
+                    check[name] = out[0, :, 3, n_xy // 3].clone()
+            e1.synchronize()
+            if it >= a.warmup:
+                ms[name].append(e0.elapsed_time(e1) / a.calls)
+    # the two legs compute the same fields (one fp32 rounding each)
+    dk, dt = check["kernel"].double(), check["torch"].double()
+    top = max(float(amp.abs().max()), float(vort.abs().max())) * v_scale
+    assert bool(((dk - dt).abs() <= 2.0 ** -22 * dt.abs() + 1e-12 * top).all())
+    res, lines = {}, []
+    for name, v in ms.items():
+        med, lo, hi = statistics.median(v), min(v), max(v)
+        res[name] = med
+        line = {"leg": name, "repeats": len(v), "calls_per_window": a.calls, "median_ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4)}
+        if name == "vorticity_amplitudes":
+            line.update(modes=1, radial_points=N + n_ext)
+        else:
+            line.update(mesh=[n_xy, n_xy, n_z], variables=10, frames=a.frames, bytes=nbytes,
+                        GB_per_s=round(nbytes / (med * 1e-3) / 1e9, 1))
+        lines.append(line)
+    lines.append({"device": torch.cuda.get_device_name(dev), "kernel_over_fill": round(res["kernel"] / res["fill"], 3),
+                  "torch_over_kernel": round(res["torch"] / res["kernel"], 2),
+                  "vorticity_amplitudes_over_kernel": round(res["vorticity_amplitudes"] / res["kernel"], 4)})
+    for line in lines:
+        print(json.dumps(line), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+    gp.close()
+    ctx.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
