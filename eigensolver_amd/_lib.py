@@ -231,6 +231,18 @@ FIELD_REFERENCE, FIELD_Z_REFERENCE_ANGLE, FIELD_BIG_ENDIAN = 1, 2, 4
 # ---- Cartesian sampling and vorticity (section 8) ----------------------------------------------------------------
 VORT_NAMES = ("Wr_C", "Wr_S", "Wphi_C", "Wphi_S", "Wz_C")                                     # ES_VORT_*
 CVAR_NAMES = ("P_T", "xi_x", "xi_y", "xi_z", "v_x", "v_y", "v_z", "vort_x", "vort_y", "vort_z")   # ES_CVAR_* (mask bits)
+# ---- perturbation fields of a slab mode (section 9) --------------------------------------------------------------
+_SLAB_FIELD_PROFILE_FIELDS = ("rho", "c2", "vA2", "U", "dU")
+
+
+class SlabFieldProfiles(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _SLAB_FIELD_PROFILE_FIELDS]
+
+
+SAMP_NAMES = ("xi_x", "xi_z", "P_T", "v_x", "v_z", "vort_y")                                  # ES_SAMP_* (complex)
+SVAR_NAMES = ("xi_x", "xi_z", "P_T", "v_x", "v_z", "vort_y")                                  # ES_SVAR_* (mask bits)
+SLAB_MODE_SAUSAGE, SLAB_MODE_KINK = 0, 1
+SLAB_FIELD_SHEAR_PT = 1
 
 
 def _sig(lib):
@@ -296,4 +308,9 @@ def _sig(lib):
     lib.es_cyl_cartesian_synthesis.argtypes = [vp, vp, vp, vp, i, i, i, d, d, vp, i, vp, i, vp, i, vp, i, C.c_uint32, d,
                                                C.c_float, i, vp]
     lib.es_cyl_cartesian_split.argtypes = [i, i, i, i] + [C.POINTER(i)] * 5
+    # (9) perturbation fields of a slab mode
+    lib.es_slab_polarisation.argtypes = [vp, vp, vp, vp, i, i, vp, vp, i, vp, vp, vp, i, C.POINTER(SlabFieldProfiles),
+                                         d, d, d, d, i, i, vp, vp]
+    lib.es_slab_field_synthesis.argtypes = [vp, vp, vp, i, i, d, d, d, vp, i, vp, i, vp, i, C.c_uint32, d, C.c_float, i,
+                                            vp]
     return lib

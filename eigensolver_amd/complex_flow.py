@@ -168,6 +168,45 @@ class SlabComplexFlow:
         x_int = torch.linspace(p.desc.x_boundary, p.desc.x_end, N, dtype=torch.float64, device=dev)
         return dict(x_int=x_int, value_int=vi, flux_int=fi, x_ext=xe, value_ext=ve, flux_ext=fe, status=st)
 
+    # ---- perturbation fields (C ABI section 9) -----------------------------------------------------------------------
+    def polarisation(self, mode, k, w, n_ext=500, reference_quirks=True):
+        """Complex amplitudes of the modes at the complex (k, omega) pairs (es_slab_polarisation on the arrays of
+        `eigenfunction`; k is broadcast against w): dict of CUDA tensors x [n, 2 n_ext + N], amp [n, 6, 2 n_ext + N]
+        (complex128, channels _lib.SAMP_NAMES) and status [n].  Every field is Re[amp e^{i (k z - w t)}], growth factor
+        e^{Im w t} included.  reference_quirks=False adds the shear term of linear theory to the "sfg" flux; the "sfx" flux
+        carries the script's own term already, so False is an error for it.  Rows that are not ES_PT_OK are NaN."""
+        import torch
+        from . import shooting
+        if not reference_quirks and self.variant == CX_SFX:
+            raise ValueError('the "sfx" flux already carries its U\' term (SF-X:401): reference_quirks=False is for "sfg"')
+        shooting._require_exterior_points(n_ext)
+        p = self.problem(mode)
+        e = self.eigenfunction(mode, k, w, n_ext=n_ext)
+        dev = e["value_int"].device
+        if isinstance(w, torch.Tensor):
+            wt = w.to(device=dev, dtype=torch.complex128).reshape(-1)
+        else:
+            wt = torch.as_tensor(np.asarray(w, dtype=complex).reshape(-1), device=dev)
+        dk = torch.broadcast_to(p._dev(k).reshape(-1), wt.shape).contiguous()
+        out = p._slab_polarisation_of(e, dk, wt.real.contiguous(), wt.imag.contiguous(), reference_quirks)
+        out["status"] = e["status"]
+        return out
+
+    def fields(self, mode, k, w, x, z, t, variables=None, v_scale=1.0, fill=float("nan"), big_endian=False,
+               frames_per_call=None, n_ext=500, reference_quirks=True):
+        """Fields of ONE complex root (k, omega) of `mode` on the mesh (x, z, t), as ShootProblem.slab_fields returns them:
+        dict of x, z, t, names, frames [n_t, n_sel, n_z, n_x] float32 and <name>: frames[:, i], or with frames_per_call a
+        generator of such dicts.  The frames grow (or decay) as e^{Im w t}."""
+        from . import shooting
+        if np.ndim(k) != 0 or np.ndim(w) != 0:
+            raise ValueError("fields() takes one root: scalar k and omega")
+        mask, names = shooting.slab_var_mask(variables)
+        tab = self.polarisation(mode, [float(k)], [complex(w)], n_ext=n_ext, reference_quirks=reference_quirks)
+        p = self.problem(mode)
+        dx, dz, dt = (p._dev(a).reshape(-1) for a in (x, z, t))
+        return shooting.slab_frames(self.ctx, tab["x"][0], tab["amp"][0], int(p.desc.n_nodes), int(n_ext), float(k),
+                                    complex(w), dx, dz, dt, names, v_scale, fill, big_endian, frames_per_call)
+
     # ---- the reference's worker signature --------------------------------------------------------------------------
     def _worker(self, mode, wavenumber, ws, ks, ws_imag, ks_imag, freq):
         freq = np.asarray(freq, dtype=complex).reshape(-1)

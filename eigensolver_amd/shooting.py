@@ -196,6 +196,112 @@ def cartesian_split(ctx, n_x, n_y, n_z, n_t):
     return dict(zip(("pieces", "z_chunk", "z_parts", "items_per_group", "groups"), (a.value for a in v)))
 
 
+def slab_var_mask(variables):
+    """Mask of es_slab_field_synthesis and the names in the order it stores them (ascending bit, _lib.SVAR_NAMES)."""
+    names = list(_lib.SVAR_NAMES) if variables is None else list(variables)
+    unknown = [v for v in names if v not in _lib.SVAR_NAMES]
+    if unknown:
+        raise ValueError(f"unknown slab field variable(s) {unknown}: choose from {_lib.SVAR_NAMES}")
+    if not names:
+        raise ValueError(f"empty list of slab field variables: choose from {_lib.SVAR_NAMES}")
+    mask = 0
+    for v in names:
+        mask |= 1 << _lib.SVAR_NAMES.index(v)
+    return mask, [v for b, v in enumerate(_lib.SVAR_NAMES) if (mask >> b) & 1]
+
+
+def slab_field_profiles(eq):
+    """The es_slab_field_profiles arrays of slab equilibrium `eq` at its N nodes (node 0 is x = -1) as NumPy arrays:
+    the equilibrium's own profiles() at every second sample (the others are the mid-points of the march), constants
+    where a family has none (the flow slab's rho, c^2, vA^2; the density slab's U = 0, U' = 0)."""
+    if not isinstance(eq, eqm._SlabBase):
+        raise ValueError("slab field profiles exist for slab equilibria only")
+    N = int(eq.n_nodes)
+    prof = eq.profiles()
+    const = {"rho": eq.rho_i0, "c2": eq.c_i0 ** 2, "vA2": eq.vA_i0 ** 2, "U": 0.0, "dU": 0.0}
+    out = {}
+    for name in _lib._SLAB_FIELD_PROFILE_FIELDS:
+        a = np.asarray(prof[name], dtype=np.float64)[::2] if name in prof else np.full(N, const[name])
+        assert a.shape == (N,)
+        out[name] = np.ascontiguousarray(a, dtype=np.float64)
+    return out
+
+
+def slab_polarisation(ctx, k, w_re, w_im, eig, prof, rho_e, vA_e, c_e, U_e, parity, flags=0):
+    """es_slab_polarisation on the arrays of an eigenfunction call.  k, w_re [n] and w_im [n] or None: CUDA float64; eig:
+    the dict of ShootProblem.eigenfunction (float64 arrays) or SlabComplexFlow.eigenfunction (complex128 arrays); prof:
+    dict of CUDA float64 arrays [N] named _lib._SLAB_FIELD_PROFILE_FIELDS.  Returns dict of CUDA tensors x [n, n_tab]
+    (float64, ascending: left exterior, interior, right exterior, n_tab = 2 n_ext + N) and amp [n, 6, n_tab]
+    (complex128, channels _lib.SAMP_NAMES).  Enqueued on the context's stream."""
+    import torch
+    vi, fi, xe, ve, fe = (eig[a] for a in ("value_int", "flux_int", "x_ext", "value_ext", "flux_ext"))
+    n, N = vi.shape
+    n_ext = xe.shape[1]
+    cplx = vi.dtype == torch.complex128
+    for a in (vi, fi, ve, fe):
+        assert a.is_cuda and a.is_contiguous() and a.dtype == (torch.complex128 if cplx else torch.float64)
+    assert fi.shape == (n, N) and ve.shape == (n, n_ext) and fe.shape == (n, n_ext) and k.shape == (n,) and w_re.shape == (n,)
+    assert w_im is None or w_im.shape == (n,)
+    assert all(prof[a].shape == (N,) and prof[a].dtype == torch.float64 for a in _lib._SLAB_FIELD_PROFILE_FIELDS)
+    fp = _lib.SlabFieldProfiles(*[prof[a].data_ptr() for a in _lib._SLAB_FIELD_PROFILE_FIELDS])
+    n_tab = N + 2 * n_ext
+    x = torch.empty((n, n_tab), dtype=torch.float64, device=vi.device)
+    amp = torch.empty((n, 6, n_tab), dtype=torch.complex128, device=vi.device)
+    P = lambda a: _lib.ptr(a) if a is not None and a.numel() else None      # noqa: E731
+    rc = ctx.lib.es_slab_polarisation(ctx.handle, P(k), P(w_re), P(w_im), n, N, P(vi), P(fi), n_ext, P(xe), P(ve), P(fe),
+                                      1 if cplx else 0, C.byref(fp), float(rho_e), float(vA_e), float(c_e), float(U_e),
+                                      int(parity), int(flags), P(x), P(amp))
+    _lib.check(ctx.handle, rc)
+    return dict(x=x, amp=amp)
+
+
+def slab_field_synthesis(ctx, xtab, amp, n_nodes, n_ext, k, w, x, z, t, variables=None, v_scale=1.0, fill=float("nan"),
+                         flags=0, out=None):
+    """es_slab_field_synthesis for the table of one mode (xtab [n_tab] float64, amp [6, n_tab] complex128, CUDA): float32
+    frames out[n_t, n_sel, n_z, n_x] in the order of slab_var_mask(variables)[1].  w may be complex.  x, z, t: CUDA float64
+    vectors.  `out`: a preallocated contiguous float32 tensor of that shape (4-byte alignment suffices).  Enqueued on the
+    context's stream; returns (out, names)."""
+    import torch
+    mask, names = slab_var_mask(variables)
+    n_tab = xtab.numel()
+    if n_tab != int(n_nodes) + 2 * int(n_ext) or tuple(amp.shape) != (6, n_tab):
+        raise ValueError(f"(n_nodes, n_ext) = ({n_nodes}, {n_ext}) does not match the table: xtab has {n_tab} points, amp "
+                         f"the shape {tuple(amp.shape)}; expected 2 n_ext + n_nodes points and (6, that)")
+    assert amp.dtype == torch.complex128
+    for a in (xtab, x, z, t):
+        assert a.is_cuda and a.dtype == torch.float64 and a.is_contiguous()
+    assert amp.is_cuda and amp.is_contiguous()
+    shape = (t.numel(), len(names), z.numel(), x.numel())
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=xtab.device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous()
+    w = complex(w)
+    rc = ctx.lib.es_slab_field_synthesis(ctx.handle, _lib.ptr(xtab), _lib.ptr(amp), int(n_nodes), int(n_ext), float(k),
+                                         w.real, w.imag, _lib.ptr(x), x.numel(), _lib.ptr(z), z.numel(), _lib.ptr(t),
+                                         t.numel(), mask, float(v_scale), float(fill), int(flags), _lib.ptr(out))
+    _lib.check(ctx.handle, rc)
+    return out, names
+
+
+def slab_frames(ctx, xtab, amp, n_nodes, n_ext, k, w, dx, dz, dt, names, v_scale, fill, big_endian, frames_per_call):
+    """The dict (or, with frames_per_call, the generator of dicts) that ShootProblem.slab_fields and
+    SlabComplexFlow.fields return, from the table of one mode."""
+    flags = _lib.FIELD_BIG_ENDIAN if big_endian else 0
+
+    def chunk(t_part):
+        out, _ = slab_field_synthesis(ctx, xtab, amp, n_nodes, n_ext, k, w, dx, dz, t_part, names, v_scale, fill, flags)
+        d = dict(x=dx, z=dz, t=t_part, names=names, frames=out)
+        d.update({v: out[:, i] for i, v in enumerate(names)})
+        return d
+
+    if frames_per_call is None:
+        return chunk(dt)
+    step = int(frames_per_call)
+    if step < 1:
+        raise ValueError("frames_per_call must be >= 1")
+    return (chunk(dt[a:a + step]) for a in range(0, dt.numel(), step))
+
+
 def make_desc(eq, mode, m=None):
     """es_shoot_desc + profile dict for equilibrium `eq` and mode "kink" / "sausage" (azimuthal order m for
     cylinders defaults to the reference's 1 / 0)."""
@@ -458,6 +564,50 @@ class ShootProblem:
         if step < 1:
             raise ValueError("frames_per_call must be >= 1")
         return (chunk(dt[a:a + step]) for a in range(0, dt.numel(), step))
+
+    def _require_slab(self):
+        if not isinstance(self.eq, eqm._SlabBase):
+            raise ValueError("slab_polarisation / slab_fields are for slab equilibria only (cylinders: polarisation, "
+                             "fields, cartesian_fields)")
+
+    def slab_field_profiles(self):
+        """slab_field_profiles(eq) of this problem's equilibrium as CUDA tensors."""
+        self._require_slab()
+        return {a: self._dev(b) for a, b in slab_field_profiles(self.eq).items()}
+
+    def _slab_polarisation_of(self, eig, dk, w_re, w_im, reference_quirks):
+        d = self.desc
+        return slab_polarisation(self.ctx, dk, w_re, w_im, eig, self.slab_field_profiles(), d.rho_e, d.vA_e, d.c_e, d.U_e,
+                                 int(d.slab_mode), 0 if reference_quirks else _lib.SLAB_FIELD_SHEAR_PT)
+
+    def slab_polarisation(self, k, w, n_ext=500, reference_quirks=True):
+        """Complex amplitudes of the slab modes at the real (k, omega) pairs (es_slab_polarisation on the arrays of
+        `eigenfunction`): dict of CUDA tensors x [n, 2 n_ext + N] (ascending: left exterior, interior, mirrored right
+        exterior, each boundary abscissa twice) and amp [n, 6, 2 n_ext + N] (complex128, channels _lib.SAMP_NAMES); every
+        field is Re[amp e^{i (k z - w t)}].  reference_quirks: the flux as the determinant uses it; False adds the shear
+        term (F/Om)(k U'/Om) Vx of linear theory to it (ES_SLAB_FIELD_SHEAR_PT).  A pair that is not ES_PT_OK gets NaN
+        amplitudes.  n_ext is 0 (no exteriors) or at least 3."""
+        self._require_slab()
+        _require_exterior_points(n_ext)
+        dk, dw = self._dev(k).reshape(-1), self._dev(w).reshape(-1)
+        return self._slab_polarisation_of(self.eigenfunction(dk, dw, n_ext=n_ext), dk, dw, None, reference_quirks)
+
+    def slab_fields(self, k, w, x, z, t, variables=None, v_scale=1.0, fill=float("nan"), big_endian=False,
+                    frames_per_call=None, n_ext=500, reference_quirks=True):
+        """Fields of ONE slab root (k, omega) on the mesh (x, z, t): float32 CUDA tensors, x fastest -- with y = [0.0] the
+        point order postprocess.write_vtk_rectilinear_frames writes.  Returns a dict
+            x [n_x], z [n_z], t [n_t], names, frames [n_t, n_sel, n_z, n_x], <name>: frames[:, i]
+        `variables` defaults to all of _lib.SVAR_NAMES and is stored in that order.  Points outside [-R, R], R = L 2 pi / k
+        (or outside [-1, 1] with n_ext = 0) carry `fill`.  frames_per_call: a generator of such dicts, at most that many
+        frames each.  v_scale multiplies v_x, v_z and vort_y.  big_endian: every float32 is byte-swapped on the device."""
+        self._require_slab()
+        if np.ndim(k) != 0 or np.ndim(w) != 0:
+            raise ValueError("slab_fields() takes one root: scalar k and omega")
+        mask, names = slab_var_mask(variables)
+        tab = self.slab_polarisation([float(k)], [float(w)], n_ext=n_ext, reference_quirks=reference_quirks)
+        dx, dz, dt = (self._dev(a).reshape(-1) for a in (x, z, t))
+        return slab_frames(self.ctx, tab["x"][0], tab["amp"][0], int(self.desc.n_nodes), int(n_ext), float(k), float(w),
+                           dx, dz, dt, names, v_scale, fill, big_endian, frames_per_call)
 
     def alloc_root_table(self, capacity):
         import torch

@@ -736,6 +736,79 @@ int es_cyl_cartesian_synthesis(es_context* ctx, const double* d_radius, const do
 int es_cyl_cartesian_split(int n_x, int n_y, int n_z, int n_t, int* pieces, int* z_chunk, int* z_parts,
                            int* items_per_group, int* groups);
 
+/* ======================================================================================================
+ * (9) Perturbation fields of a slab mode, real or unstable -- stages three and four for the slab families, which the
+ *     reference leaves at the two curves (Vx, P_T) (complex_imag_flow_analysis.py:1050-1072).  Equilibrium B0(x) z,
+ *     rho(x), U(x) z on |x| <= 1, uniform outside, nothing depends on y; every perturbation is
+ *     Re[A(x) e^{i (k z - w t)}] with w = w_re + i w_im and a COMPLEX amplitude A(x).
+ *
+ *     es_slab_polarisation: (V, Pf) = (value, flux) of es_shoot_eigenfunction (complex_input = 0: real arrays, d_w_im may
+ *     be NULL) or of es_complex_eigenfunction (complex_input = 1: interleaved (re, im) pairs) -> six complex amplitudes.
+ *     With Om = w - k U, S = c^2 + vA^2, q = c^2/S, cT^2 = c^2 vA^2/S (the reference's P_T is i times the physical
+ *     total-pressure amplitude):
+ *       v_x    = V                          xi_x = i V / Om                      P_T = -i Pf
+ *       xi_z   = k q Pf / (rho (Om^2 - k^2 cT^2))
+ *       v_z    = -i (Om xi_z + U' V / Om)
+ *       vort_y = i k v_x - d(v_z)/dx        (d_z v_x - d_x v_z)
+ *     The exterior uses rho_e, c_e, vA_e, U_e and U' = 0.  ES_SLAB_FIELD_SHEAR_PT first adds (F/Om)(k U'/Om) V to the
+ *     interior Pf, F = rho S (Om^2 - k^2 cT^2)/(Om^2 - k^2 c^2): the flux of linear theory, where SF-G's determinant has
+ *     (F/Om) Vx' alone.  (The ES_CX_SFX flux carries that term already: do not set the flag for it.)
+ *     Table of a mode: n_tab = 2 n_ext + N abscissae, ascending -- left exterior [-R, -1] as d_ext_x gives it, interior
+ *     x_j = -1 + j (2/(N-1)) with x_{N-1} = +1 (numpy.linspace), right exterior [1, R], the mirror image of the left one
+ *     under the far-end condition Vx(+1) = sigma Vx(-1), sigma = -1 (ES_SLAB_MODE_SAUSAGE) / +1 (ES_SLAB_MODE_KINK):
+ *     v_x, xi_x, vort_y take the factor sigma, P_T, xi_z, v_z the factor -sigma.  Each boundary abscissa appears twice.
+ *     d_x[i * n_tab + j]; d_amp[((i * 6 + c) * n_tab + j) * 2 + {0: re, 1: im}], channels c = ES_SAMP_*.
+ *     d(v_z)/dx is np.gradient(a, x, edge_order=2), coefficient form and order of operations as in section 8, of the real
+ *     and the imaginary part separately and of each of the three regions on its own -- never across x = -1 or +1, where
+ *     v_z jumps -- in a second launch of the same call.  N >= 3; n_ext = 0 leaves both exteriors out, n_ext = 1 or 2 is
+ *     an argument error.
+ *     A mode whose eigenfunction rows are NaN gets NaN amplitudes (complex NaNs: with real input a part that is
+ *     identically zero stays zero; every value synthesised from them is NaN); its d_x row is written and the other modes
+ *     do not depend on it.  Nodes where Om, Om^2 - k^2 cT^2 or Om^2 - k^2 c^2 vanish give inf / NaN at the nodes their stencil
+ *     touches and nowhere else: no guard, as in section 7.  n == 0 touches nothing.  Asynchronous on the context's stream.
+ * ====================================================================================================== */
+/* Device arrays at the N interior nodes (node 0 is x = -1), all required. */
+typedef struct es_slab_field_profiles {
+  const double* rho; const double* c2; const double* vA2; const double* U; const double* dU;
+} es_slab_field_profiles;
+
+enum { ES_SAMP_XI_X = 0, ES_SAMP_XI_Z, ES_SAMP_P_T, ES_SAMP_V_X, ES_SAMP_V_Z, ES_SAMP_VORT_Y, ES_SAMP_COUNT };
+enum { ES_SLAB_FIELD_SHEAR_PT = 1 };       /* es_slab_polarisation: Pf += (F/Om)(k U'/Om) V before anything is formed */
+
+int es_slab_polarisation(es_context* ctx, const double* d_k, const double* d_w_re,
+                         const double* d_w_im /* may be NULL: real modes */, int n,
+                         int n_nodes, const double* d_int_value, const double* d_int_flux,    /* n x N [x 2]       */
+                         int n_ext, const double* d_ext_x /* n x n_ext */,
+                         const double* d_ext_value, const double* d_ext_flux,                 /* n x n_ext [x 2]   */
+                         int complex_input, const es_slab_field_profiles* profiles,
+                         double rho_e, double vA_e, double c_e, double U_e, int parity /* ES_SLAB_MODE_* */, int flags,
+                         double* d_x /* n x n_tab */, double* d_amp /* n x 6 x n_tab x 2 */);
+
+/* es_slab_field_synthesis: the table of ONE mode -> frames on the (x, z, t) mesh, float32.
+ *   d_xtab [n_tab], d_amp [6 x n_tab x 2] as es_slab_polarisation writes them for one mode, n_tab = 2 n_ext + n_nodes;
+ *   d_x [n_x], d_z [n_z], d_t [n_t].  var_mask selects by bit (ES_SVAR_*), n_sel variables stored in ascending bit order.
+ *   With E = e^{w_im t}, C = cos(k z - w_re t), S = sin(k z - w_re t) and A the interpolated amplitude the value is
+ *     E (A_re C - A_im S)         (formed as A_re (E C) - A_im (E S), fp64, rounded once to float32)
+ *   v_scale multiplies v_x, v_z and vort_y.
+ *   Region, decided by the tabulated abscissae (-R = xtab[0], -1 = xtab[n_ext], +1 = xtab[n_ext + N - 1], R = last):
+ *     -1 <= x <= 1     interior            -R <= x < -1     left exterior            1 < x <= R     right exterior
+ *   Inside a region the bracketing points are found by bisection (no spacing is assumed) and the real and the imaginary
+ *   part are A_j + (A_j+1 - A_j) (x - x_j) / (x_j+1 - x_j); exactly on the last node of a region that node's value.
+ *   Everything else -- points outside [-R, R], NaN coordinates, an exterior that is absent -- gets `fill` in every
+ *   selected variable, as bits (a NaN keeps its payload), byte-swapped if requested.
+ *   d_out [n_t][n_sel][n_z][n_x] float32, x fastest: with y = [0] the point order of a legacy-VTK RECTILINEAR_GRID.
+ *   flags: ES_FIELD_BIG_ENDIAN only.  d_out needs 4-byte alignment only: rows are written with 16-byte stores when every
+ *   row starts on a 16-byte boundary (n_x a multiple of 4, d_out 16-byte aligned), with 4-byte stores otherwise, the same
+ *   bits either way.  Indices are size_t; n_z * n_t and n_x must each be below 2^31.
+ *   n_x, n_z or n_t == 0: nothing to write, ES_SUCCESS.  An empty or unknown mask, n_nodes < 3, n_ext of 1 or 2 and a
+ *   misaligned d_out are argument errors.  Asynchronous on the context's stream, no host read-back (the first call with a
+ *   larger (z, t) table grows the context's scratch, which synchronises). */
+enum { ES_SVAR_XI_X = 0, ES_SVAR_XI_Z, ES_SVAR_P_T, ES_SVAR_V_X, ES_SVAR_V_Z, ES_SVAR_VORT_Y, ES_SVAR_COUNT };
+int es_slab_field_synthesis(es_context* ctx, const double* d_xtab, const double* d_amp /* 6 x n_tab x 2 */,
+                            int n_nodes, int n_ext, double k, double w_re, double w_im,
+                            const double* d_x, int n_x, const double* d_z, int n_z, const double* d_t, int n_t,
+                            uint32_t var_mask, double v_scale, float fill, int flags, float* d_out);
+
 #ifdef __cplusplus
 }
 #endif
