@@ -313,4 +313,6 @@ def _sig(lib):
                                          d, d, d, d, i, i, vp, vp]
     lib.es_slab_field_synthesis.argtypes = [vp, vp, vp, i, i, d, d, d, vp, i, vp, i, vp, i, C.c_uint32, d, C.c_float, i,
                                             vp]
+    # (10) branch labels
+    lib.es_shoot_mode_signature.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
     return lib

@@ -16,26 +16,6 @@
 namespace {
 using namespace es_shoot_shared;
 
-// forward RK4 step of one state vector (u, v):  y' = A y
-template <bool DIAG>
-__device__ __forceinline__ void rk4_step_forward(double& u, double& v, const Coef& A0, const Coef& Am, const Coef& A1,
-                                                 double h, double h2, double h6, double h3) {
-#define ES_RHS_F(A, uu, vv, ku, kv)                                              \
-  if (DIAG) { ku = fma(A.a11, uu, A.a12 * vv); kv = fma(A.a22, vv, A.a21 * uu); } \
-  else      { ku = A.a12 * vv;                 kv = A.a21 * uu; }
-  double k1u, k1v, k2u, k2v, k3u, k3v, k4u, k4v, tu, tv;
-  ES_RHS_F(A0, u, v, k1u, k1v);
-  tu = fma(h2, k1u, u); tv = fma(h2, k1v, v);
-  ES_RHS_F(Am, tu, tv, k2u, k2v);
-  tu = fma(h2, k2u, u); tv = fma(h2, k2v, v);
-  ES_RHS_F(Am, tu, tv, k3u, k3v);
-  tu = fma(h, k3u, u); tv = fma(h, k3v, v);
-  ES_RHS_F(A1, tu, tv, k4u, k4v);
-  u = fma(h6, k1u + k4u, fma(h3, k2u + k3u, u));
-  v = fma(h6, k1v + k4v, fma(h3, k2v + k3v, v));
-#undef ES_RHS_F
-}
-
 template <int FAM>
 __global__ __launch_bounds__(64) void eigen_interior_kernel(ShootDev P, const double* __restrict__ kv,
                                                             const double* __restrict__ wv, int n,

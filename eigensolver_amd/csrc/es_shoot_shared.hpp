@@ -64,6 +64,27 @@ __device__ __forceinline__ void finish_point(const ShootDev& P, const Mismatch& 
   if (crossed) st = ES_PT_CONTINUUM;
 }
 
+// forward RK4 step of one state vector (u, v):  y' = A y  (the writing march of es_eigenfunction.hip, the reducing march of
+// es_signature.hip)
+template <bool DIAG>
+__device__ __forceinline__ void rk4_step_forward(double& u, double& v, const Coef& A0, const Coef& Am, const Coef& A1,
+                                                 double h, double h2, double h6, double h3) {
+#define ES_RHS_F(A, uu, vv, ku, kv)                                              \
+  if (DIAG) { ku = fma(A.a11, uu, A.a12 * vv); kv = fma(A.a22, vv, A.a21 * uu); } \
+  else      { ku = A.a12 * vv;                 kv = A.a21 * uu; }
+  double k1u, k1v, k2u, k2v, k3u, k3v, k4u, k4v, tu, tv;
+  ES_RHS_F(A0, u, v, k1u, k1v);
+  tu = fma(h2, k1u, u); tv = fma(h2, k1v, v);
+  ES_RHS_F(Am, tu, tv, k2u, k2v);
+  tu = fma(h2, k2u, u); tv = fma(h2, k2v, v);
+  ES_RHS_F(Am, tu, tv, k3u, k3v);
+  tu = fma(h, k3u, u); tv = fma(h, k3v, v);
+  ES_RHS_F(A1, tu, tv, k4u, k4v);
+  u = fma(h6, k1u + k4u, fma(h3, k2u + k3u, u));
+  v = fma(h6, k1v + k4v, fma(h3, k2v + k3v, v));
+#undef ES_RHS_F
+}
+
 // One (k, omega) pair per lane, unrelated k per lane.  Must be called by ALL threads of the workgroup together (it
 // contains barriers): the k-independent base table is staged chunk by chunk (CH RK4 steps) in the LDS buffer `sb`
 // (FamTraits<FAM>::NB * (2 CH + 1) doubles, point-major) with coalesced loads, and every lane then reads the same

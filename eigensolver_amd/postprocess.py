@@ -64,6 +64,28 @@ def from_root_table(roots, accepted_only=True):
     return w, k
 
 
+def _host(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def split_by_signature(roots, sig, accepted_only=True):
+    """Root table + its ShootProblem.label_roots signature -> {(nodes_value, nodes_flux): (omegas, ks)}, one k-sorted curve
+    (sort_by_wavenumber) per branch label: what the analysis scripts cut out with hand-picked phase-speed cut-offs per data
+    set (fast_sausage_branch1/2/3, ..., :244-372).  Each entry is ready for fit_branch; {"kink": entry} for pickle_layout.
+    accepted_only drops the entries with flag == 0 and the pairs that are not ES_PT_OK (label (-1, -1))."""
+    w, k = _host(roots["w"]).astype(np.float64), _host(roots["k"]).astype(np.float64)
+    nv, nf, st = (_host(a).astype(np.int64) for a in (sig.nodes_value, sig.nodes_flux, sig.status))
+    assert len(w) == len(k) == len(nv) == len(nf) == len(st), "the signature must be aligned with the table"
+    keep = np.ones(len(w), dtype=bool)
+    if accepted_only:
+        keep = (_host(roots["flag"]) == 1) & (st == 0)
+    out = {}
+    for label in sorted(set(zip(nv[keep].tolist(), nf[keep].tolist()))):
+        sel = keep & (nv == label[0]) & (nf == label[1])
+        out[label] = sort_by_wavenumber(w[sel], k[sel])
+    return out
+
+
 def write_vtk(dump_file, x, y, z, variables, names):
     """Legacy-VTK structured-grid dump of scalar fields on an irregular grid, byte for byte what the reference's
     `makeDumpVTK(x, y, z, variables, varList, dumpFile)` writes (Cylinder/Non-uniform density/Coronal/Movies/

@@ -26,6 +26,18 @@ class ScreenCounts(NamedTuple):
     overflow: bool      # count > capacity: only the first `capacity` brackets were written and refined
 
 
+class ModeSignature(NamedTuple):
+    """es_shoot_mode_signature: one entry per (k, omega) pair, CUDA tensors.  (nodes_value, nodes_flux) is the branch label
+    of a root; a pair that is not PT_OK carries -1 in the four integer fields and NaN in the two peaks."""
+    nodes_value: object       # int32: sign changes of value (P / Vx) over the interior nodes
+    nodes_flux: object        # int32: sign changes of flux (xi_r / P_T)
+    peak_node_value: object   # int32: smallest node index that attains max|value| (node 0 = boundary)
+    peak_node_flux: object
+    peak_value: object        # float64: max|value|, exterior boundary value = +-1 (1.0 at node 0: a surface-like mode)
+    peak_flux: object
+    status: object            # uint8: PT_* of the exterior
+
+
 def read_screen_counts(counts, capacity):
     """Read the four count words once (a CUDA tensor: this is the host synchronisation the async calls leave to the
     caller; a CPU tensor works the same).  Raises EsError, naming the failure of the synchronous call's
@@ -436,6 +448,34 @@ class ShootProblem:
         _lib.check(self.ctx.handle, rc)
         x_int = torch.linspace(self.desc.x_boundary, self.desc.x_end, N, dtype=torch.float64, device=dev)
         return dict(x_int=x_int, value_int=vi, flux_int=fi, x_ext=xe, value_ext=ve, flux_ext=fe)
+
+    def mode_signature(self, k, w, count=None):
+        """es_shoot_mode_signature at the (k, omega) pairs: the sign changes of the interior value and flux rows of
+        `eigenfunction`, their peaks and the nodes of the peaks, reduced inside the march -> ModeSignature.  Nothing is
+        written per node and nothing is read back.  count: an int32 CUDA tensor of one element holding the number of valid
+        pairs (the count word of find_roots_async, or the four words of the screened searches, whose first is the count);
+        entries past min(count, n) are left as allocated."""
+        import torch
+        dk, dw = self._dev(k).reshape(-1), self._dev(w).reshape(-1)
+        n = dk.numel()
+        assert dw.numel() == n
+        if count is not None:
+            assert count.is_cuda and count.numel() >= 1 and count.dtype == torch.int32
+        ints = [torch.empty(n, dtype=torch.int32, device=dk.device) for _ in range(4)]
+        peaks = [torch.empty(n, dtype=torch.float64, device=dk.device) for _ in range(2)]
+        st = torch.empty(n, dtype=torch.uint8, device=dk.device)
+        rc = self.ctx.lib.es_shoot_mode_signature(self.ctx.handle, self.handle, _lib.ptr(dk), _lib.ptr(dw), n,
+                                                  _lib.ptr(count) if count is not None else None,
+                                                  *[_lib.ptr(t) for t in ints + peaks], _lib.ptr(st))
+        _lib.check(self.ctx.handle, rc)
+        return ModeSignature(*ints, *peaks, st)
+
+    def label_roots(self, roots, count=None):
+        """ModeSignature of every entry of a root table: `roots` is the dict find_roots / find_roots_mixed return, or the
+        (dict, RootTable) of alloc_root_table filled by an _async search together with its device count word (no read-back:
+        the launch is sized for the capacity and takes the count on the device)."""
+        t = roots[0] if isinstance(roots, tuple) else roots
+        return self.mode_signature(t["k"], t["w"], count=count)
 
     def _require_positive_cylinder(self):
         if not isinstance(self.eq, eqm._CylinderBase):

@@ -809,6 +809,45 @@ int es_slab_field_synthesis(es_context* ctx, const double* d_xtab, const double*
                             const double* d_x, int n_x, const double* d_z, int n_z, const double* d_t, int n_t,
                             uint32_t var_mask, double v_scale, float fill, int flags, float* d_out);
 
+/* ======================================================================================================
+ * (10) Branch label of a root: the radial node count of its eigenfunction.  The grid search returns a cloud of (k, omega)
+ *     and every stage after it (sections 5, 7, 8, 9) takes ONE chosen root; the reference cuts the cloud into branches by
+ *     hand, with phase-speed bands and cut-offs picked per data set
+ *       Cylinder/Non-uniform flow/Coronal/Eigenfunctions/analysis_cylinder_flow_coronal.py :244-372
+ *     (fast_sausage_branch1/2/3, slow_body_kink, ...).  What those cuts stand for is the pair (sign changes of value, sign
+ *     changes of flux) over the interior nodes, with whether the mode peaks at the interface (surface-like) or inside
+ *     (body): constant along a dispersion branch, different between neighbouring branches.
+ *
+ *     es_shoot_mode_signature: one (k, omega) pair per lane, the interior algorithm of es_shoot_eigenfunction (cylinders:
+ *     two columns from the axis node out to the boundary, then the state marched out again; slabs: adjoint march, then the
+ *     forward march) with `value` and `flux` exactly as section 5 defines them -- but nothing is written per node: the rows
+ *     are reduced in registers and each pair gets one entry per output.
+ *       d_nodes_value / d_nodes_flux [n]: sign changes of the row over the N interior nodes in output order (node 0 =
+ *         boundary).  Entries that are exactly zero or NaN are skipped (the kink axis node of an untwisted cylinder is
+ *         exactly 0.0: its target is 0); a change is counted whenever the sign of an entry differs from the sign of the last
+ *         entry that was kept.
+ *       d_peak_value / d_peak_flux [n]: max |entry| over the N nodes in the normalisation of section 5 (exterior value at
+ *         the boundary = +-1; NaN entries are skipped, a row without any other entry gives NaN and node -1);
+ *         d_peak_node_value / d_peak_node_flux [n]: the smallest node index that attains it.  peak_value = 1 at node 0 for
+ *         a cylinder: the pressure perturbation is largest on the interface.
+ *       d_status [n]: ES_PT_* of the exterior as es_shoot_eigenfunction sees it (ES_PT_OK, ES_PT_LEAKY, ES_PT_NONFINITE;
+ *         ES_PT_CONTINUUM is not looked at, as in section 5).  A pair that is not ES_PT_OK gets -1 in the four integer
+ *         outputs and NaN in the two peaks; the other pairs do not depend on it.
+ *     Any of the seven output pointers may be NULL: that output is skipped.
+ *     d_count (may be NULL): a device word holding the number of valid pairs -- the d_count of es_shoot_find_roots_async or
+ *     d_counts[0] of the screened searches, with table->d_k / table->d_w as the pairs.  The launch is sized for n, the
+ *     kernel uses min(max(*d_count, 0), n) and entries beyond it are left alone: no read-back between search and labels.
+ *     Asynchronous on the context's stream, no host synchronisation.  n == 0 succeeds and touches nothing (the arrays may
+ *     then be NULL).  ES_ERR_INVALID_ARG: n < 0, a null problem, d_k or d_w null with n > 0; ES_ERR_UNSUPPORTED: an unknown
+ *     family.  Not offered: complex frequencies (section 6), the closed-form uniform cylinder (section 4) and the exterior
+ *     -- the closed-form exterior of a bound mode has no node of interest.
+ * ====================================================================================================== */
+int es_shoot_mode_signature(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w, int n,
+                            const int32_t* d_count /* may be NULL */,
+                            int32_t* d_nodes_value, int32_t* d_nodes_flux,
+                            int32_t* d_peak_node_value, int32_t* d_peak_node_flux,
+                            double* d_peak_value, double* d_peak_flux, uint8_t* d_status);
+
 #ifdef __cplusplus
 }
 #endif
