@@ -8,13 +8,12 @@
 //                                 (mode, radial point); derivatives by three-point formulas per region
 //   es_cyl_cartesian_synthesis    amplitudes of one mode -> float32 frames [t][variable][z][y][x]; the (x, y) stage
 //                                 (hypot, search, interpolation) once per point, then bound by store bandwidth
-#include "es_common.hpp"
+#include "es_field_shared.hpp"
 
 namespace {
 
 // ---- v amplitudes -> amplitudes of curl v ---------------------------------------------------------------------------
-// d/dr is np.gradient(a, r, edge_order=2) of each region on its own, coefficient form and order of operations included:
-// nodes p, p+1, p+2 with spacings d1, d2; the node differentiated is the middle one, or the first / last at a region end.
+// d/dr is np.gradient(a, r, edge_order=2) of each region on its own (gradient_stencil).
 __global__ __launch_bounds__(256) void vorticity_amplitudes_kernel(const double* __restrict__ radius,
                                                                   const double* __restrict__ amp,
                                                                   const double* __restrict__ kk, int n, int N, int n_ext,
@@ -27,30 +26,14 @@ __global__ __launch_bounds__(256) void vorticity_amplitudes_kernel(const double*
   const int base = (j < N) ? 0 : N;
   const int len = (j < N) ? N : n_ext;                 // >= 3 (checked by the host)
   const int q = j - base;
-  int p = q - 1;
-  if (p < 0) p = 0;
-  if (p > len - 3) p = len - 3;
   const double* r = radius + i * n_r + base;
   const double* A = amp + i * (size_t)ES_AMP_COUNT * n_r + base;
-  const double d1 = r[p + 1] - r[p], d2 = r[p + 2] - r[p + 1];
-  double c0, c1, c2;
-  if (q == 0) {
-    c0 = -(2.0 * d1 + d2) / (d1 * (d1 + d2));
-    c1 = (d1 + d2) / (d1 * d2);
-    c2 = -d1 / (d2 * (d1 + d2));
-  } else if (q == len - 1) {
-    c0 = d2 / (d1 * (d1 + d2));
-    c1 = -(d2 + d1) / (d1 * d2);
-    c2 = (2.0 * d2 + d1) / (d2 * (d1 + d2));
-  } else {
-    c0 = -d2 / (d1 * (d1 + d2));
-    c1 = (d2 - d1) / (d1 * d2);
-    c2 = d1 / (d2 * (d1 + d2));
-  }
+  const Stencil3 g = gradient_stencil(r, q, len);
+  const int p = g.p;
   const double* az = A + (size_t)ES_AMP_V_Z * n_r;
   const double* ap = A + (size_t)ES_AMP_V_PHI * n_r;
-  const double d_az = (c0 * az[p] + c1 * az[p + 1]) + c2 * az[p + 2];
-  const double d_ap = (c0 * ap[p] + c1 * ap[p + 1]) + c2 * ap[p + 2];
+  const double d_az = (g.c0 * az[p] + g.c1 * az[p + 1]) + g.c2 * az[p + 2];
+  const double d_ap = (g.c0 * ap[p] + g.c1 * ap[p + 1]) + g.c2 * ap[p + 2];
   const double rq = r[q], a_r = A[(size_t)ES_AMP_V_R * n_r + q], a_p = ap[q], a_z = az[q], k = kk[i];
   double* V = vort + i * (size_t)ES_VORT_COUNT * n_r + j;
   V[ES_VORT_R_C * n_r] = -(dm * a_z) / rq;
@@ -61,19 +44,6 @@ __global__ __launch_bounds__(256) void vorticity_amplitudes_kernel(const double*
 }
 
 // ---- amplitudes -> frames on the (x, y, z, t) mesh ------------------------------------------------------------------
-// cos(k z_l - w t_tau) at [tau * n_z + l], sin of the same behind it at [n_z n_t + tau * n_z + l]
-__global__ __launch_bounds__(256) void cartesian_tables_kernel(const double* __restrict__ z, int n_z,
-                                                              const double* __restrict__ tt, int n_t, double k, double w,
-                                                              double* __restrict__ tab) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t n_zt = (size_t)n_z * n_t;
-  if (i >= n_zt) return;
-  const size_t tau = i / n_z, l = i - tau * n_z;
-  const double ph = k * z[l] - w * tt[tau];
-  tab[i] = cos(ph);
-  tab[n_zt + i] = sin(ph);
-}
-
 struct CartArgs {
   const double* radius; const double* amp; const double* vort;   // [n_r], [7 x n_r], [5 x n_r] (NULL without vorticity)
   const double* x; const double* y;
@@ -85,11 +55,6 @@ struct CartArgs {
   uint32_t mask, fill_bits;                            // fill as it is stored (already byte-swapped if requested)
   double v_scale;
 };
-
-__device__ __forceinline__ uint32_t f32_bits(double v, bool swap) {
-  const uint32_t u = __float_as_uint((float)v);        // the one rounding to fp32
-  return swap ? __builtin_bswap32(u) : u;
-}
 
 constexpr uint32_t bit(int v) { return 1u << v; }
 
@@ -146,16 +111,7 @@ __global__ __launch_bounds__(64) void cartesian_synthesis_kernel(CartArgs a, con
     valid |= (ok ? 1u : 0u) << e;
   }
   if (!live) return;
-  // largest j of the region with rad[j] <= r, at most the last but one: the four searches of a lane side by side
-  for (int it = 0; it < a.iters; ++it) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (hi[e] - lo[e] > 1) {
-        const int mid = (lo[e] + hi[e]) >> 1;
-        if (rad[mid] <= rr[e]) lo[e] = mid; else hi[e] = mid;
-      }
-    }
-  }
+  bracket4(rad, rr, lo, hi, a.iters);                  // largest j of the region with rad[j] <= r, at most the last but one
   double cC[ES_CVAR_COUNT][4], cS[2][4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -164,13 +120,10 @@ __global__ __launch_bounds__(64) void cartesian_synthesis_kernel(CartArgs a, con
     cS[0][e] = 0.0; cS[1][e] = 0.0;
     if (!((valid >> e) & 1u)) continue;
     const int j = lo[e];
-    const double r = rr[e], r0 = rad[j], r1 = rad[j + 1];
-    const double tt = (r - r0) / (r1 - r0);
-    const bool at_end = r >= r1;                       // only on the last node of a region: that node's value
+    const double r = rr[e];
+    const Lerp lerp(r, rad[j], rad[j + 1]);
     auto L = [&](const double* __restrict__ tabv, int c) {
-      const double A0 = tabv[(size_t)c * n_r + j], A1 = tabv[(size_t)c * n_r + j + 1];
-      const double v = A0 + (A1 - A0) * tt;
-      return at_end ? A1 : v;
+      return lerp(tabv[(size_t)c * n_r + j], tabv[(size_t)c * n_r + j + 1]);
     };
     const double ct = xv[e] / r, st = yv[e] / r;
     double cm = 1.0, sm = 0.0;                         // cos(m theta), sin(m theta) by angle addition
@@ -228,17 +181,8 @@ __global__ __launch_bounds__(64) void cartesian_synthesis_kernel(CartArgs a, con
 #pragma unroll
           for (int e = 0; e < 4; ++e) b[e] = f32_bits(cC[v][e] * C, SWAP);
         }
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (!((valid >> e) & 1u)) b[e] = a.fill_bits;
-        uint32_t* dst = out + (plane + l) * a.n_pts;
-        if (WIDE) {                                    // n_pts is a multiple of 4: a lane has all four points or none
-          *reinterpret_cast<uint4*>(dst + pt[0]) = make_uint4(b[0], b[1], b[2], b[3]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if ((live >> e) & 1u) dst[pt[e]] = b[e];
-        }
+        fill_invalid(b, valid, a.fill_bits);
+        store4<WIDE>(out + (plane + l) * a.n_pts, pt, b, live);
       }
     }
   }
@@ -314,23 +258,16 @@ extern "C" int es_cyl_cartesian_synthesis(es_context* ctx, const double* d_radiu
   if (n_x == 0 || n_y == 0 || n_z == 0 || n_t == 0) return ES_SUCCESS;
   ES_REQUIRE(ctx, d_radius && d_amp && d_x && d_y && d_z && d_t && d_out, "null pointer");
   ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t n_zt = (size_t)n_z * n_t;
-  int rc = es_ensure_scratch(ctx, 2 * n_zt * sizeof(double));
+  double* tab;
+  int rc = zt_tables<false>(ctx, d_z, n_z, d_t, n_t, k, w, 0.0, &tab);
   if (rc) return rc;
-  double* tab = static_cast<double*>(ctx->d_scratch);
-  hipLaunchKernelGGL(cartesian_tables_kernel, dim3((unsigned)((n_zt + 255) / 256)), dim3(256), 0, ctx->stream, d_z, n_z,
-                     d_t, n_t, k, w, tab);
-  ES_HIP_CHECK(ctx, hipGetLastError());
   const bool swap = (flags & ES_FIELD_BIG_ENDIAN) != 0;
   CartArgs a;
   a.radius = d_radius; a.amp = d_amp; a.vort = d_vort; a.x = d_x; a.y = d_y;
   a.N = n_nodes; a.n_ext = n_ext; a.m = m; a.n_x = n_x; a.n_z = n_z; a.n_t = n_t;
   a.n_sel = __builtin_popcount(var_mask);
-  const int longest = n_nodes > n_ext ? n_nodes : n_ext;
-  a.iters = 0;
-  while ((1ll << a.iters) < (long long)longest - 1) ++a.iters;
-  memcpy(&a.fill_bits, &fill, sizeof(fill));           // as bits: a NaN keeps its payload
-  if (swap) a.fill_bits = __builtin_bswap32(a.fill_bits);
+  a.iters = bisection_iters(n_nodes > n_ext ? n_nodes : n_ext);
+  a.fill_bits = fill_bits_of(fill, swap);
   a.mask = var_mask; a.v_scale = v_scale;
   a.n_pts = (size_t)n_x * (size_t)n_y;
   int pieces, groups;
@@ -341,10 +278,8 @@ extern "C" int es_cyl_cartesian_synthesis(es_context* ctx, const double* d_radiu
   const bool wide = (a.n_pts % 4 == 0) && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
   const dim3 grid((unsigned)gx, gy), block(64);
   uint32_t* out = reinterpret_cast<uint32_t*>(d_out);
-  if (swap && wide) hipLaunchKernelGGL((cartesian_synthesis_kernel<true, true>), grid, block, 0, ctx->stream, a, tab, out);
-  else if (swap) hipLaunchKernelGGL((cartesian_synthesis_kernel<true, false>), grid, block, 0, ctx->stream, a, tab, out);
-  else if (wide) hipLaunchKernelGGL((cartesian_synthesis_kernel<false, true>), grid, block, 0, ctx->stream, a, tab, out);
-  else hipLaunchKernelGGL((cartesian_synthesis_kernel<false, false>), grid, block, 0, ctx->stream, a, tab, out);
+  auto kernel = ES_SWAP_WIDE_KERNEL(cartesian_synthesis_kernel, swap, wide);
+  hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, a, tab, out);
   ES_HIP_CHECK(ctx, hipGetLastError());
   return ES_SUCCESS;
 }

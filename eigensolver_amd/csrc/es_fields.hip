@@ -12,7 +12,7 @@
 //   4. the z-components get the angular factor -sin(m theta) (:940)                          -> ES_FIELD_Z_REFERENCE_ANGLE
 // The density perturbation of the scripts is not computed (step of np.gradient that is not the grid's, division by
 // time[t]: :854-863, :950).
-#include "es_common.hpp"
+#include "es_field_shared.hpp"
 
 namespace {
 
@@ -108,10 +108,7 @@ __global__ __launch_bounds__(256) void field_tables_kernel(const double* __restr
   }
 }
 
-__device__ __forceinline__ float to_f32(double v, bool swap) {
-  const float f = (float)v;                            // the one rounding to fp32
-  return swap ? __uint_as_float(__builtin_bswap32(__float_as_uint(f))) : f;
-}
+__device__ __forceinline__ float to_f32(double v, bool swap) { return __uint_as_float(f32_bits(v, swap)); }
 
 // One wave per workgroup; lane l owns the four radial columns c0 + 4 l .. c0 + 4 l + 3 of a 256-column chunk and keeps
 // their amplitudes in registers.  blockIdx.y walks the (z, t) pairs, blockIdx.z chunks of theta rows; every row of every

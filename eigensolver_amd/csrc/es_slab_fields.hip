@@ -8,7 +8,7 @@
 //                             (np.gradient's three-point formulas) for vort_y
 //   es_slab_field_synthesis   the table of one mode -> frames [t][variable][z][x]; the x stage (search, interpolation)
 //                             once per workgroup, then bound by store bandwidth
-#include "es_common.hpp"
+#include "es_field_shared.hpp"
 
 // workgroups (of one wave) es_slab_field_synthesis asks for; a build flag so that tools can time other values
 #ifndef ES_SLAB_SYNTH_WAVES
@@ -93,8 +93,8 @@ __global__ __launch_bounds__(256) void slab_field_polarisation_kernel(SlabPolArg
   put(ES_SAMP_V_Z, v_z);
 }
 
-// vort_y = i k v_x - d(v_z)/dx.  d/dx is np.gradient(a, x, edge_order=2) of each of the three regions on its own,
-// coefficient form and order of operations included (es_cartesian.hip): nodes p, p+1, p+2 with spacings d1, d2.
+// vort_y = i k v_x - d(v_z)/dx.  d/dx is np.gradient(a, x, edge_order=2) of each of the three regions on its own
+// (gradient_stencil).
 __global__ __launch_bounds__(256) void slab_field_vorticity_kernel(const double* __restrict__ xs,
                                                                    double* __restrict__ amp,
                                                                    const double* __restrict__ kk, int n, int N,
@@ -106,30 +106,12 @@ __global__ __launch_bounds__(256) void slab_field_vorticity_kernel(const double*
   const int j = (int)(t - i * n_tab);
   const int base = (j < n_ext) ? 0 : (j < n_ext + N ? n_ext : n_ext + N);
   const int len = (base == n_ext) ? N : n_ext;         // >= 3 (checked by the host)
-  const int qn = j - base;
-  int p = qn - 1;
-  if (p < 0) p = 0;
-  if (p > len - 3) p = len - 3;
-  const double* x = xs + i * n_tab + base;
-  const double d1 = x[p + 1] - x[p], d2 = x[p + 2] - x[p + 1];
-  double c0, c1, c2;
-  if (qn == 0) {
-    c0 = -(2.0 * d1 + d2) / (d1 * (d1 + d2));
-    c1 = (d1 + d2) / (d1 * d2);
-    c2 = -d1 / (d2 * (d1 + d2));
-  } else if (qn == len - 1) {
-    c0 = d2 / (d1 * (d1 + d2));
-    c1 = -(d2 + d1) / (d1 * d2);
-    c2 = (2.0 * d2 + d1) / (d2 * (d1 + d2));
-  } else {
-    c0 = -d2 / (d1 * (d1 + d2));
-    c1 = (d2 - d1) / (d1 * d2);
-    c2 = d1 / (d2 * (d1 + d2));
-  }
+  const Stencil3 g = gradient_stencil(xs + i * n_tab + base, j - base, len);
+  const int p = g.p;
   double* A = amp + i * (size_t)ES_SAMP_COUNT * n_tab * 2;
   const double* vz = A + ((size_t)ES_SAMP_V_Z * n_tab + base) * 2;
-  const double d_re = (c0 * vz[2 * p] + c1 * vz[2 * p + 2]) + c2 * vz[2 * p + 4];
-  const double d_im = (c0 * vz[2 * p + 1] + c1 * vz[2 * p + 3]) + c2 * vz[2 * p + 5];
+  const double d_re = (g.c0 * vz[2 * p] + g.c1 * vz[2 * p + 2]) + g.c2 * vz[2 * p + 4];
+  const double d_im = (g.c0 * vz[2 * p + 1] + g.c1 * vz[2 * p + 3]) + g.c2 * vz[2 * p + 5];
   const double* vx = A + ((size_t)ES_SAMP_V_X * n_tab + j) * 2;
   const double k = kk[i];
   double* o = A + ((size_t)ES_SAMP_VORT_Y * n_tab + j) * 2;
@@ -138,20 +120,6 @@ __global__ __launch_bounds__(256) void slab_field_vorticity_kernel(const double*
 }
 
 // ---- table -> frames on the (x, z, t) mesh --------------------------------------------------------------------------------
-// e^{w_im t_tau} cos(k z_l - w_re t_tau) at [tau * n_z + l], the same with sin behind it at [n_z n_t + tau * n_z + l]
-__global__ __launch_bounds__(256) void slab_field_tables_kernel(const double* __restrict__ z, int n_z,
-                                                                const double* __restrict__ tt, int n_t, double k,
-                                                                double w_re, double w_im, double* __restrict__ tab) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t n_zt = (size_t)n_z * n_t;
-  if (i >= n_zt) return;
-  const size_t tau = i / n_z, l = i - tau * n_z;
-  const double ph = k * z[l] - w_re * tt[tau];
-  const double E = exp(w_im * tt[tau]);
-  tab[i] = E * cos(ph);
-  tab[n_zt + i] = E * sin(ph);
-}
-
 struct SlabSynArgs {
   const double* xtab; const double* amp;               // [n_tab], [6 x n_tab x 2]
   const double* x;
@@ -162,11 +130,6 @@ struct SlabSynArgs {
   uint32_t mask, fill_bits;                            // fill as it is stored (already byte-swapped if requested)
   double v_scale;
 };
-
-__device__ __forceinline__ uint32_t slab_f32_bits(double v, bool swap) {
-  const uint32_t u = __float_as_uint((float)v);        // the one rounding to fp32
-  return swap ? __builtin_bswap32(u) : u;
-}
 
 // One wave per workgroup: it owns 256 x columns, four per lane, finds once their region, bracket and the interpolated
 // (A_re, A_im) of every selected variable, keeps them in registers and walks its share of the (frame, z) rows -- runs of
@@ -209,16 +172,7 @@ __global__ __launch_bounds__(64) void slab_field_synthesis_kernel(SlabSynArgs a,
     valid |= (ok ? 1u : 0u) << e;
   }
   if (!live) return;
-  // largest j of the region with xtab[j] <= x, at most the last but one: the four searches of a lane side by side
-  for (int it = 0; it < a.iters; ++it) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (hi[e] - lo[e] > 1) {
-        const int mid = (lo[e] + hi[e]) >> 1;
-        if (xt[mid] <= xv[e]) lo[e] = mid; else hi[e] = mid;
-      }
-    }
-  }
+  bracket4(xt, xv, lo, hi, a.iters);                   // largest j of the region with xtab[j] <= x, at most the last but one
   double Are[ES_SVAR_COUNT][4], Aim[ES_SVAR_COUNT][4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -226,17 +180,14 @@ __global__ __launch_bounds__(64) void slab_field_synthesis_kernel(SlabSynArgs a,
     for (int v = 0; v < ES_SVAR_COUNT; ++v) { Are[v][e] = 0.0; Aim[v][e] = 0.0; }
     if (!((valid >> e) & 1u)) continue;
     const int j = lo[e];
-    const double x0 = xt[j], x1 = xt[j + 1];
-    const double tt = (xv[e] - x0) / (x1 - x0);
-    const bool at_end = xv[e] >= x1;                   // only on the last node of a region: that node's value
+    const Lerp lerp(xv[e], xt[j], xt[j + 1]);
 #pragma unroll
     for (int v = 0; v < ES_SVAR_COUNT; ++v) {
       if (!((mask >> v) & 1u)) continue;
       const double* __restrict__ p = a.amp + ((size_t)v * n_tab + j) * 2;   // ES_SVAR_* and ES_SAMP_* share their order
       const double s = (v == ES_SVAR_V_X || v == ES_SVAR_V_Z || v == ES_SVAR_VORT_Y) ? a.v_scale : 1.0;
-      const double re = p[0] + (p[2] - p[0]) * tt, im = p[1] + (p[3] - p[1]) * tt;
-      Are[v][e] = (at_end ? p[2] : re) * s;
-      Aim[v][e] = (at_end ? p[3] : im) * s;
+      Are[v][e] = lerp(p[0], p[2]) * s;
+      Aim[v][e] = lerp(p[1], p[3]) * s;
     }
   }
 
@@ -258,18 +209,9 @@ __global__ __launch_bounds__(64) void slab_field_synthesis_kernel(SlabSynArgs a,
         const double EC = tab[row], ES = tab[a.n_zt + row];
         uint32_t b[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) b[e] = slab_f32_bits(Are[v][e] * EC - Aim[v][e] * ES, SWAP);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (!((valid >> e) & 1u)) b[e] = a.fill_bits;
-        uint32_t* dst = out + (plane + l) * (size_t)a.n_x;
-        if (WIDE) {                                    // n_x is a multiple of 4: a lane has all four columns or none
-          *reinterpret_cast<uint4*>(dst + col[0]) = make_uint4(b[0], b[1], b[2], b[3]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if ((live >> e) & 1u) dst[col[e]] = b[e];
-        }
+        for (int e = 0; e < 4; ++e) b[e] = f32_bits(Are[v][e] * EC - Aim[v][e] * ES, SWAP);
+        fill_invalid(b, valid, a.fill_bits);
+        store4<WIDE>(out + (plane + l) * (size_t)a.n_x, col, b, live);
       }
     }
     zt += l1 - l0;
@@ -336,22 +278,16 @@ extern "C" int es_slab_field_synthesis(es_context* ctx, const double* d_xtab, co
   ES_REQUIRE(ctx, d_xtab && d_amp && d_x && d_z && d_t && d_out, "null pointer");
   ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const size_t n_zt = (size_t)n_z * n_t;
-  int rc = es_ensure_scratch(ctx, 2 * n_zt * sizeof(double));
+  double* tab;
+  const int rc = zt_tables<true>(ctx, d_z, n_z, d_t, n_t, k, w_re, w_im, &tab);
   if (rc) return rc;
-  double* tab = static_cast<double*>(ctx->d_scratch);
-  hipLaunchKernelGGL(slab_field_tables_kernel, dim3((unsigned)((n_zt + 255) / 256)), dim3(256), 0, ctx->stream, d_z, n_z, d_t,
-                     n_t, k, w_re, w_im, tab);
-  ES_HIP_CHECK(ctx, hipGetLastError());
   const bool swap = (flags & ES_FIELD_BIG_ENDIAN) != 0;
   SlabSynArgs a;
   a.xtab = d_xtab; a.amp = d_amp; a.x = d_x;
   a.N = n_nodes; a.n_ext = n_ext; a.n_x = n_x; a.n_z = n_z; a.n_zt = n_zt;
   a.n_sel = __builtin_popcount(var_mask);
-  const int longest = n_nodes > n_ext ? n_nodes : n_ext;
-  a.iters = 0;
-  while ((1ll << a.iters) < (long long)longest - 1) ++a.iters;
-  memcpy(&a.fill_bits, &fill, sizeof(fill));           // as bits: a NaN keeps its payload
-  if (swap) a.fill_bits = __builtin_bswap32(a.fill_bits);
+  a.iters = bisection_iters(n_nodes > n_ext ? n_nodes : n_ext);
+  a.fill_bits = fill_bits_of(fill, swap);
   a.mask = var_mask; a.v_scale = v_scale;
   // workgroups over (chunk of 256 columns, group of rows): about 16 waves per CU, and no more, because each workgroup
   // repeats the x stage of its columns
@@ -364,8 +300,7 @@ extern "C" int es_slab_field_synthesis(es_context* ctx, const double* d_xtab, co
   const bool wide = (n_x % 4 == 0) && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
   const dim3 grid((unsigned)gx, (unsigned)gy), block(64);
   uint32_t* out = reinterpret_cast<uint32_t*>(d_out);
-  auto kernel = swap ? (wide ? slab_field_synthesis_kernel<true, true> : slab_field_synthesis_kernel<true, false>)
-                     : (wide ? slab_field_synthesis_kernel<false, true> : slab_field_synthesis_kernel<false, false>);
+  auto kernel = ES_SWAP_WIDE_KERNEL(slab_field_synthesis_kernel, swap, wide);
   hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, a, tab, out);
   ES_HIP_CHECK(ctx, hipGetLastError());
   return ES_SUCCESS;

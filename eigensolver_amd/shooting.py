@@ -84,16 +84,55 @@ def audit_arrays(ctx, D_scr, st_scr, D64, st64, rel64=None, capacity=1024, rows=
                             full_row(cells // max(nw, 1)), cells % max(nw, 1), kinds)
 
 
-def var_mask(variables):
-    """Mask of es_cyl_field_synthesis and the names in the order it stores them (ascending bit, _lib.VAR_NAMES)."""
-    names = list(_lib.VAR_NAMES) if variables is None else list(variables)
-    unknown = [v for v in names if v not in _lib.VAR_NAMES]
+def _mask_of(table, variables, what):
+    """Bit mask of `variables` (None: all) over the name tuple `table` and the names in ascending bit order, the order
+    in which a synthesis call stores them."""
+    names = list(table) if variables is None else list(variables)
+    unknown = [v for v in names if v not in table]
     if unknown:
-        raise ValueError(f"unknown field variable(s) {unknown}: choose from {_lib.VAR_NAMES}")
+        raise ValueError(f"unknown {what}(s) {unknown}: choose from {table}")
     mask = 0
     for v in names:
-        mask |= 1 << _lib.VAR_NAMES.index(v)
-    return mask, [v for b, v in enumerate(_lib.VAR_NAMES) if (mask >> b) & 1]
+        mask |= 1 << table.index(v)
+    return mask, [v for b, v in enumerate(table) if (mask >> b) & 1]
+
+
+def _frames_out(out, shape, device):
+    """The float32 frames tensor of a synthesis call: allocated, or the caller's `out` checked."""
+    import torch
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous()
+    return out
+
+
+def _frame_chunks(synth, t, frames_per_call, names, **mesh):
+    """The dict of a fields call (mesh entries, t, names, frames, <name>: frames[:, i]), or with frames_per_call the
+    generator of such dicts, at most that many frames each.  synth(t_part, carry) -> (frames, carry); carry is a dict of
+    further entries that a chunk hands on to the next one (None before the first)."""
+    def one(t_part, carry):
+        out, carry = synth(t_part, carry)
+        d = dict(carry, **mesh, t=t_part, names=names, frames=out)
+        d.update({v: out[:, i] for i, v in enumerate(names)})
+        return d, carry
+
+    if frames_per_call is None:
+        return one(t, None)[0]
+    step = int(frames_per_call)
+    if step < 1:
+        raise ValueError("frames_per_call must be >= 1")
+
+    def chunks():
+        carry = None
+        for a in range(0, t.numel(), step):
+            d, carry = one(t[a:a + step], carry)
+            yield d
+    return chunks()
+
+
+def var_mask(variables):
+    """Mask of es_cyl_field_synthesis and the names in the order it stores them (ascending bit, _lib.VAR_NAMES)."""
+    return _mask_of(_lib.VAR_NAMES, variables, "field variable")
 
 
 def field_profiles(eq, r, reference_quirks=True):
@@ -127,10 +166,7 @@ def field_synthesis(ctx, radius, amp, m, k, w, theta, z, t, variables=None, v_sc
     mask, names = var_mask(variables)
     n_r, n_theta, n_z, n_t = radius.numel(), theta.numel(), z.numel(), t.numel()
     assert amp.shape == (7, n_r) and amp.dtype == torch.float64 and radius.dtype == torch.float64
-    shape = (n_t, len(names), n_z, n_theta, n_r)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=radius.device)
-    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous()
+    out = _frames_out(out, (n_t, len(names), n_z, n_theta, n_r), radius.device)
     pts = torch.empty((n_z, n_theta, n_r, 3), dtype=torch.float32, device=radius.device) if want_points else None
     rc = ctx.lib.es_cyl_field_synthesis(ctx.handle, _lib.ptr(radius), _lib.ptr(amp), n_r, int(m), float(k), float(w),
                                         _lib.ptr(theta), n_theta, _lib.ptr(z), n_z, _lib.ptr(t), n_t, mask,
@@ -142,14 +178,7 @@ def field_synthesis(ctx, radius, amp, m, k, w, theta, z, t, variables=None, v_sc
 
 def cartesian_var_mask(variables):
     """Mask of es_cyl_cartesian_synthesis and the names in the order it stores them (ascending bit, _lib.CVAR_NAMES)."""
-    names = list(_lib.CVAR_NAMES) if variables is None else list(variables)
-    unknown = [v for v in names if v not in _lib.CVAR_NAMES]
-    if unknown:
-        raise ValueError(f"unknown Cartesian field variable(s) {unknown}: choose from {_lib.CVAR_NAMES}")
-    mask = 0
-    for v in names:
-        mask |= 1 << _lib.CVAR_NAMES.index(v)
-    return mask, [v for b, v in enumerate(_lib.CVAR_NAMES) if (mask >> b) & 1]
+    return _mask_of(_lib.CVAR_NAMES, variables, "Cartesian field variable")
 
 
 def vorticity_amplitudes(ctx, radius, amp, n_nodes, n_ext, m, k):
@@ -180,10 +209,7 @@ def cartesian_synthesis(ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z
     assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (7, n_r) and (vort is None or vort.shape == (5, n_r))
     for a in (radius, amp, vort, x, y, z, t):
         assert a is None or (a.is_cuda and a.dtype == torch.float64 and a.is_contiguous())
-    shape = (t.numel(), len(names), z.numel(), y.numel(), x.numel())
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=radius.device)
-    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous()
+    out = _frames_out(out, (t.numel(), len(names), z.numel(), y.numel(), x.numel()), radius.device)
     rc = ctx.lib.es_cyl_cartesian_synthesis(ctx.handle, _lib.ptr(radius), _lib.ptr(amp),
                                             _lib.ptr(vort) if vort is not None else None, int(n_nodes), int(n_ext),
                                             int(m), float(k), float(w), _lib.ptr(x), x.numel(), _lib.ptr(y), y.numel(),
@@ -210,16 +236,10 @@ def cartesian_split(ctx, n_x, n_y, n_z, n_t):
 
 def slab_var_mask(variables):
     """Mask of es_slab_field_synthesis and the names in the order it stores them (ascending bit, _lib.SVAR_NAMES)."""
-    names = list(_lib.SVAR_NAMES) if variables is None else list(variables)
-    unknown = [v for v in names if v not in _lib.SVAR_NAMES]
-    if unknown:
-        raise ValueError(f"unknown slab field variable(s) {unknown}: choose from {_lib.SVAR_NAMES}")
+    mask, names = _mask_of(_lib.SVAR_NAMES, variables, "slab field variable")
     if not names:
         raise ValueError(f"empty list of slab field variables: choose from {_lib.SVAR_NAMES}")
-    mask = 0
-    for v in names:
-        mask |= 1 << _lib.SVAR_NAMES.index(v)
-    return mask, [v for b, v in enumerate(_lib.SVAR_NAMES) if (mask >> b) & 1]
+    return mask, names
 
 
 def slab_field_profiles(eq):
@@ -283,10 +303,7 @@ def slab_field_synthesis(ctx, xtab, amp, n_nodes, n_ext, k, w, x, z, t, variable
     for a in (xtab, x, z, t):
         assert a.is_cuda and a.dtype == torch.float64 and a.is_contiguous()
     assert amp.is_cuda and amp.is_contiguous()
-    shape = (t.numel(), len(names), z.numel(), x.numel())
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=xtab.device)
-    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous()
+    out = _frames_out(out, (t.numel(), len(names), z.numel(), x.numel()), xtab.device)
     w = complex(w)
     rc = ctx.lib.es_slab_field_synthesis(ctx.handle, _lib.ptr(xtab), _lib.ptr(amp), int(n_nodes), int(n_ext), float(k),
                                          w.real, w.imag, _lib.ptr(x), x.numel(), _lib.ptr(z), z.numel(), _lib.ptr(t),
@@ -300,18 +317,10 @@ def slab_frames(ctx, xtab, amp, n_nodes, n_ext, k, w, dx, dz, dt, names, v_scale
     SlabComplexFlow.fields return, from the table of one mode."""
     flags = _lib.FIELD_BIG_ENDIAN if big_endian else 0
 
-    def chunk(t_part):
-        out, _ = slab_field_synthesis(ctx, xtab, amp, n_nodes, n_ext, k, w, dx, dz, t_part, names, v_scale, fill, flags)
-        d = dict(x=dx, z=dz, t=t_part, names=names, frames=out)
-        d.update({v: out[:, i] for i, v in enumerate(names)})
-        return d
+    def synth(t_part, _):
+        return slab_field_synthesis(ctx, xtab, amp, n_nodes, n_ext, k, w, dx, dz, t_part, names, v_scale, fill, flags)[0], {}
 
-    if frames_per_call is None:
-        return chunk(dt)
-    step = int(frames_per_call)
-    if step < 1:
-        raise ValueError("frames_per_call must be >= 1")
-    return (chunk(dt[a:a + step]) for a in range(0, dt.numel(), step))
+    return _frame_chunks(synth, dt, frames_per_call, names, x=dx, z=dz)
 
 
 def make_desc(eq, mode, m=None):
@@ -531,26 +540,12 @@ class ShootProblem:
         dth, dz, dt = (self._dev(a).reshape(-1) for a in (theta, z, t))
         flags = (_lib.FIELD_Z_REFERENCE_ANGLE if reference_quirks else 0) | (_lib.FIELD_BIG_ENDIAN if big_endian else 0)
 
-        def chunk(t_part, points):
+        def synth(t_part, carry):                     # the points are produced once and handed to the later chunks
             out, pts, _ = field_synthesis(self.ctx, radius, amp, int(self.desc.m), k, w, dth, dz, t_part, names, v_scale,
-                                          flags, want_points=points is None)
-            d = dict(points=pts if points is None else points, t=t_part, names=names, frames=out)
-            d.update({v: out[:, i] for i, v in enumerate(names)})
-            return d
+                                          flags, want_points=carry is None)
+            return out, carry or dict(points=pts)
 
-        if frames_per_call is None:
-            return chunk(dt, None)
-        step = int(frames_per_call)
-        if step < 1:
-            raise ValueError("frames_per_call must be >= 1")
-
-        def chunks():
-            points = None
-            for a in range(0, dt.numel(), step):
-                d = chunk(dt[a:a + step], points)
-                points = d["points"]
-                yield d
-        return chunks()
+        return _frame_chunks(synth, dt, frames_per_call, names)
 
     def vorticity_amplitudes(self, k, w, n_ext=500, reference_quirks=False):
         """`polarisation` followed by es_cyl_vorticity_amplitudes: dict of CUDA tensors radius [n, n_r], amp [n, 7, n_r] and
@@ -591,19 +586,11 @@ class ShootProblem:
         dx, dy, dz, dt = (self._dev(a).reshape(-1) for a in (x, y, z, t))
         flags = _lib.FIELD_BIG_ENDIAN if big_endian else 0
 
-        def chunk(t_part):
-            out, _ = cartesian_synthesis(self.ctx, radius, amp, vort, int(self.desc.n_nodes), int(n_ext), int(self.desc.m),
-                                         k, w, dx, dy, dz, t_part, names, v_scale, fill, flags)
-            d = dict(x=dx, y=dy, z=dz, t=t_part, names=names, frames=out)
-            d.update({v: out[:, i] for i, v in enumerate(names)})
-            return d
+        def synth(t_part, _):
+            return cartesian_synthesis(self.ctx, radius, amp, vort, int(self.desc.n_nodes), int(n_ext), int(self.desc.m),
+                                       k, w, dx, dy, dz, t_part, names, v_scale, fill, flags)[0], {}
 
-        if frames_per_call is None:
-            return chunk(dt)
-        step = int(frames_per_call)
-        if step < 1:
-            raise ValueError("frames_per_call must be >= 1")
-        return (chunk(dt[a:a + step]) for a in range(0, dt.numel(), step))
+        return _frame_chunks(synth, dt, frames_per_call, names, x=dx, y=dy, z=dz)
 
     def _require_slab(self):
         if not isinstance(self.eq, eqm._SlabBase):

@@ -15,16 +15,15 @@ by repeat in one process so that drift hits all alike:
 Per leg one JSON line: median / min / max ms over the repeats and GB/s of the median; then the ratios kernel / fill and
 torch / kernel, and the time of one es_cyl_vorticity_amplitudes call (one mode, 1 200 radial points).
 
-    python tools/time_cartesian_synthesis.py [--repeats 20] [--warmup 3] [--frames 8] [--nxy 267] [--calls 1] [--out profiles/cartesian_synthesis_timing.jsonl]
+    python tools/time_cartesian_synthesis.py [--repeats 20] [--warmup 3] [--frames 8] [--nxy 267] [--calls 1] [--lib PATH] [--out profiles/cartesian_synthesis_timing.jsonl]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import synthesis_timing  # noqa: E402  (tools/, beside this file)
 
 
 def torch_fields(torch, radius, amp, vort, N, m, k, w, x, y, z, t, v_scale, fill, out):
@@ -70,22 +69,12 @@ def torch_fields(torch, radius, amp, vort, N, m, k, w, x, y, z, t, v_scale, fill
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--frames", type=int, default=8)
+    synthesis_timing.add_common_arguments(ap)
     ap.add_argument("--nxy", type=int, default=267, help="points along x and along y (267: the reference's slice)")
-    ap.add_argument("--calls", type=int, default=1, help="calls per timed window (times are per call); above 1 the host's "
-                    "launch latency hides behind the previous call")
-    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
-    assert a.repeats >= 10, "at least 10 timed repeats per leg"
+    torch, dev, stream, ctx = synthesis_timing.open_context(a)
     import numpy as np
-    import torch
-    from eigensolver_amd import ShootProblem, _lib, equilibrium as q, shooting
-    assert torch.cuda.is_available(), "this tool measures on the GPU; there is nothing to fall back to"
-    dev = torch.device("cuda", torch.cuda.current_device())
-    stream = torch.cuda.Stream(device=dev)
-    ctx = _lib.Context(dev.index or 0, stream=stream)
+    from eigensolver_amd import ShootProblem, equilibrium as q, shooting
     k, w, v_scale, fill = 1.2, 3.741567685037965, 25.0, 0.0
     N, n_ext, n_xy, n_z = 500, 700, a.nxy, 31
     with torch.cuda.stream(stream):
@@ -99,7 +88,6 @@ def main():
         m = int(gp.desc.m)
         out = torch.empty((a.frames, 10, n_z, n_xy, n_xy), dtype=torch.float32, device=dev)
         kk = T([k])
-    nbytes = out.numel() * 4
     legs = {
         "kernel": lambda: shooting.cartesian_synthesis(ctx, radius, amp, vort, N, n_ext, m, k, w, x, y, z, t, None, v_scale,
                                                        fill, 0, out=out),
@@ -107,46 +95,11 @@ def main():
         "fill": lambda: out.fill_(1.0),
         "vorticity_amplitudes": lambda: shooting.vorticity_amplitudes(ctx, tab["radius"], tab["amp"], N, n_ext, m, kk),
     }
-    ms = {name: [] for name in legs}
-    check = {}
-    for it in range(a.warmup + a.repeats):
-        for name, run in legs.items():
-            with torch.cuda.stream(stream):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                for _ in range(a.calls):
-                    run()
-                e1.record(stream)
-                if it == 0 and name in ("kernel", "torch"):
-                    check[name] = out[0, :, 3, n_xy // 3].clone()
-            e1.synchronize()
-            if it >= a.warmup:
-                ms[name].append(e0.elapsed_time(e1) / a.calls)
-    # the two legs compute the same fields (one fp32 rounding each)
-    dk, dt = check["kernel"].double(), check["torch"].double()
-    top = max(float(amp.abs().max()), float(vort.abs().max())) * v_scale
-    assert bool(((dk - dt).abs() <= 2.0 ** -22 * dt.abs() + 1e-12 * top).all())
-    res, lines = {}, []
-    for name, v in ms.items():
-        med, lo, hi = statistics.median(v), min(v), max(v)
-        res[name] = med
-        line = {"leg": name, "repeats": len(v), "calls_per_window": a.calls, "median_ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4)}
-        if name == "vorticity_amplitudes":
-            line.update(modes=1, radial_points=N + n_ext)
-        else:
-            line.update(mesh=[n_xy, n_xy, n_z], variables=10, frames=a.frames, bytes=nbytes,
-                        GB_per_s=round(nbytes / (med * 1e-3) / 1e9, 1))
-        lines.append(line)
-    lines.append({"device": torch.cuda.get_device_name(dev), "kernel_over_fill": round(res["kernel"] / res["fill"], 3),
-                  "torch_over_kernel": round(res["torch"] / res["kernel"], 2),
-                  "vorticity_amplitudes_over_kernel": round(res["vorticity_amplitudes"] / res["kernel"], 4)})
-    for line in lines:
-        print(json.dumps(line), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+    ms, check = synthesis_timing.measure(torch, stream, a, legs, lambda: out[0, :, 3, n_xy // 3])
+    synthesis_timing.assert_same_fields(check, max(float(amp.abs().max()), float(vort.abs().max())) * v_scale)
+    synthesis_timing.report(a, torch.cuda.get_device_name(dev), ms, out.numel() * 4,
+                            dict(mesh=[n_xy, n_xy, n_z], variables=10),
+                            "vorticity_amplitudes", dict(modes=1, radial_points=N + n_ext))
     gp.close()
     ctx.close()
     return 0

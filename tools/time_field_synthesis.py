@@ -15,16 +15,15 @@ Per leg one JSON line: median / min / max ms over the repeats and GB/s of the me
 torch / kernel, and the time of one ShootProblem.polarisation call (es_shoot_eigenfunction + es_cyl_polarisation for one
 mode, 1 200 radial points).
 
-    python tools/time_field_synthesis.py [--repeats 20] [--warmup 3] [--frames 8]
+    python tools/time_field_synthesis.py [--repeats 20] [--warmup 3] [--frames 8] [--calls 1] [--lib PATH] [--out profiles/field_synthesis_timing.jsonl]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import synthesis_timing  # noqa: E402  (tools/, beside this file)
 
 VARLIST = ["xi_r", "xi_phi", "P_T", "v_r", "v_phi", "xi_x", "xi_y", "v_x", "v_y", "v_z"]      # Export_vtk.py:986 less density
 
@@ -47,18 +46,11 @@ def torch_fields(torch, radius, amp, m, k, w, theta, z, t, v_scale, out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--frames", type=int, default=8)
+    synthesis_timing.add_common_arguments(ap)
     a = ap.parse_args()
-    assert a.repeats >= 10, "at least 10 timed repeats per leg"
+    torch, dev, stream, ctx = synthesis_timing.open_context(a)
     import numpy as np
-    import torch
     from eigensolver_amd import ShootProblem, _lib, equilibrium as q, shooting
-    assert torch.cuda.is_available(), "this tool measures on the GPU; there is nothing to fall back to"
-    dev = torch.device("cuda", torch.cuda.current_device())
-    stream = torch.cuda.Stream(device=dev)
-    ctx = _lib.Context(dev.index or 0, stream=stream)
     k, w, v_scale = 1.2, 3.741567685037965, 25.0
     with torch.cuda.stream(stream):
         gp = ShootProblem(q.CylinderDensity(width=0.9, r_sign=1.0, n_nodes=500, ic=(1e-8, 1e-8)), "kink", ctx=ctx)
@@ -70,7 +62,6 @@ def main():
         t = T(np.linspace(0.01, 2.0 * np.pi, 80)[:a.frames])
         n_r, m = radius.numel(), int(gp.desc.m)
         out = torch.empty((a.frames, len(VARLIST), 16, 60, n_r), dtype=torch.float32, device=dev)
-    nbytes = out.numel() * 4
     flags = _lib.FIELD_Z_REFERENCE_ANGLE
     legs = {
         "kernel": lambda: shooting.field_synthesis(ctx, radius, amp, m, k, w, theta, z, t, VARLIST, v_scale, flags,
@@ -79,37 +70,11 @@ def main():
         "fill": lambda: out.fill_(1.0),
         "polarisation": lambda: gp.polarisation([k], [w], n_ext=700),
     }
-    ms = {name: [] for name in legs}
-    check = {}
-    for it in range(a.warmup + a.repeats):
-        for name, run in legs.items():
-            with torch.cuda.stream(stream):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                run()
-                e1.record(stream)
-                if it == 0 and name in ("kernel", "torch"):
-                    check[name] = out[0, :, 3, 7].clone()
-            e1.synchronize()
-            if it >= a.warmup:
-                ms[name].append(e0.elapsed_time(e1))
-    # the two legs compute the same fields (one fp32 rounding each)
-    dk, dt = check["kernel"].double(), check["torch"].double()
-    assert bool(((dk - dt).abs() <= 2.0 ** -22 * dt.abs() + 1e-12 * float(amp.abs().max()) * v_scale).all())
-    res = {}
-    for name, v in ms.items():
-        med, lo, hi = statistics.median(v), min(v), max(v)
-        res[name] = med
-        line = {"leg": name, "repeats": len(v), "median_ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4)}
-        if name == "polarisation":
-            line.update(modes=1, radial_points=n_r)
-        else:
-            line.update(mesh=[n_r, 60, 16], variables=len(VARLIST), frames=a.frames, bytes=nbytes,
-                        GB_per_s=round(nbytes / (med * 1e-3) / 1e9, 1))
-        print(json.dumps(line), flush=True)
-    print(json.dumps({"device": torch.cuda.get_device_name(dev), "kernel_over_fill": round(res["kernel"] / res["fill"], 3),
-                      "torch_over_kernel": round(res["torch"] / res["kernel"], 2),
-                      "polarisation_over_kernel": round(res["polarisation"] / res["kernel"], 4)}), flush=True)
+    ms, check = synthesis_timing.measure(torch, stream, a, legs, lambda: out[0, :, 3, 7])
+    synthesis_timing.assert_same_fields(check, float(amp.abs().max()) * v_scale)
+    synthesis_timing.report(a, torch.cuda.get_device_name(dev), ms, out.numel() * 4,
+                            dict(mesh=[n_r, 60, 16], variables=len(VARLIST)),
+                            "polarisation", dict(modes=1, radial_points=n_r))
     gp.close()
     ctx.close()
     return 0

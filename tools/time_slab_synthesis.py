@@ -15,16 +15,15 @@ alike:
 Per leg one JSON line: median / min / max ms over the repeats and GB/s of the median; then the ratios kernel / fill and
 torch / kernel, and the time of one es_slab_polarisation call (one mode, 1 500 table points, both launches).
 
-    python tools/time_slab_synthesis.py [--repeats 20] [--warmup 3] [--frames 8] [--nx 1024] [--nz 512] [--calls 1] [--out profiles/slab_synthesis_timing.jsonl]
+    python tools/time_slab_synthesis.py [--repeats 20] [--warmup 3] [--frames 8] [--nx 1024] [--nz 512] [--calls 1] [--lib PATH] [--out profiles/slab_synthesis_timing.jsonl]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import synthesis_timing  # noqa: E402  (tools/, beside this file)
 
 
 def torch_fields(torch, xtab, amp, N, n_ext, k, w, x, z, t, v_scale, fill, out):
@@ -57,25 +56,13 @@ def torch_fields(torch, xtab, amp, N, n_ext, k, w, x, z, t, v_scale, fill, out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--frames", type=int, default=8)
+    synthesis_timing.add_common_arguments(ap)
     ap.add_argument("--nx", type=int, default=1024)
     ap.add_argument("--nz", type=int, default=512)
-    ap.add_argument("--calls", type=int, default=1, help="calls per timed window (times are per call); above 1 the host's "
-                    "launch latency hides behind the previous call")
-    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
-    ap.add_argument("--lib", default=None, help="another build of the library to time, e.g. one made with "
-                    "ES_BUILD_EXTRA_FLAGS=-DES_SLAB_SYNTH_WAVES=1024 (its path goes into the JSON lines)")
     a = ap.parse_args()
-    assert a.repeats >= 10, "at least 10 timed repeats per leg"
+    torch, dev, stream, ctx = synthesis_timing.open_context(a)
     import numpy as np
-    import torch
-    from eigensolver_amd import SlabComplexFlow, _lib, shooting
-    assert torch.cuda.is_available(), "this tool measures on the GPU; there is nothing to fall back to"
-    dev = torch.device("cuda", torch.cuda.current_device())
-    stream = torch.cuda.Stream(device=dev)
-    ctx = _lib.Context(dev.index or 0, stream=stream, lib=_lib.load_variant(a.lib) if a.lib else None)
+    from eigensolver_amd import SlabComplexFlow, shooting
     k, w, v_scale, fill = 0.5, 0.2 + 0.1j, 25.0, 0.0
     N, n_ext, n_x, n_z = 500, 500, a.nx, a.nz
     with torch.cuda.stream(stream):
@@ -95,7 +82,6 @@ def main():
         prof = p.slab_field_profiles()
         kk, wre, wim = T([k]), T([w.real]), T([w.imag])
         d = p.desc
-    nbytes = out.numel() * 4
     legs = {
         "kernel": lambda: shooting.slab_field_synthesis(ctx, xtab, amp, N, n_ext, k, w, x, z, t, None, v_scale, fill, 0,
                                                         out=out),
@@ -104,47 +90,10 @@ def main():
         "polarisation": lambda: shooting.slab_polarisation(ctx, kk, wre, wim, eig, prof, d.rho_e, d.vA_e, d.c_e, d.U_e,
                                                            int(d.slab_mode), 0),
     }
-    ms = {name: [] for name in legs}
-    check = {}
-    for it in range(a.warmup + a.repeats):
-        for name, run in legs.items():
-            with torch.cuda.stream(stream):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                for _ in range(a.calls):
-                    run()
-                e1.record(stream)
-                if it == 0 and name in ("kernel", "torch"):
-                    check[name] = out[:, :, n_z // 3].clone()
-            e1.synchronize()
-            if it >= a.warmup:
-                ms[name].append(e0.elapsed_time(e1) / a.calls)
-    # the two legs compute the same fields (one fp32 rounding each)
-    dk, dt = check["kernel"].double(), check["torch"].double()
-    top = float(amp.abs().max()) * v_scale * float(np.exp(abs(w.imag) * float(t.max())))
-    assert bool(((dk - dt).abs() <= 2.0 ** -22 * dt.abs() + 1e-12 * top).all())
-    res, lines = {}, []
-    for name, v in ms.items():
-        med, lo, hi = statistics.median(v), min(v), max(v)
-        res[name] = med
-        line = {"leg": name, "repeats": len(v), "calls_per_window": a.calls, "median_ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4)}
-        if name == "polarisation":
-            line.update(modes=1, table_points=N + 2 * n_ext)
-        else:
-            line.update(mesh=[n_x, n_z], variables=6, frames=a.frames, bytes=nbytes,
-                        GB_per_s=round(nbytes / (med * 1e-3) / 1e9, 1))
-        lines.append(line)
-    lines.append({"device": torch.cuda.get_device_name(dev), "lib": os.path.basename(a.lib) if a.lib else "default",
-                  "kernel_over_fill": round(res["kernel"] / res["fill"], 3),
-                  "torch_over_kernel": round(res["torch"] / res["kernel"], 2),
-                  "polarisation_over_kernel": round(res["polarisation"] / res["kernel"], 4)})
-    for line in lines:
-        print(json.dumps(line), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+    ms, check = synthesis_timing.measure(torch, stream, a, legs, lambda: out[:, :, n_z // 3])
+    synthesis_timing.assert_same_fields(check, float(amp.abs().max()) * v_scale * float(np.exp(abs(w.imag) * float(t.max()))))
+    synthesis_timing.report(a, torch.cuda.get_device_name(dev), ms, out.numel() * 4, dict(mesh=[n_x, n_z], variables=6),
+                            "polarisation", dict(modes=1, table_points=N + 2 * n_ext))
     flow.close()
     ctx.close()
     return 0
