@@ -315,4 +315,6 @@ def _sig(lib):
                                             vp]
     # (10) branch labels
     lib.es_shoot_mode_signature.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    # (11) dispersion slopes
+    lib.es_shoot_root_slopes.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp]
     return lib

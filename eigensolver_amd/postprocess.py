@@ -86,6 +86,53 @@ def split_by_signature(roots, sig, accepted_only=True):
     return out
 
 
+def curves_with_slopes(roots, sig, slopes, accepted_only=True):
+    """split_by_signature with the group speed riding along: root table + its label_roots signature + its root_slopes
+    (ShootProblem.root_slopes, or anything with group_velocity and status) -> {label: (omegas, ks, cg)}, each curve ordered
+    by k (ties by omega).  accepted_only drops the entries with flag == 0 and the pairs either call did not find ES_PT_OK."""
+    w, k = _host(roots["w"]).astype(np.float64), _host(roots["k"]).astype(np.float64)
+    nv, nf, st = (_host(a).astype(np.int64) for a in (sig.nodes_value, sig.nodes_flux, sig.status))
+    cg, st2 = _host(slopes.group_velocity).astype(np.float64), _host(slopes.status).astype(np.int64)
+    assert len(w) == len(k) == len(nv) == len(nf) == len(st) == len(cg) == len(st2), \
+        "signature and slopes must be aligned with the table"
+    keep = np.ones(len(w), dtype=bool)
+    if accepted_only:
+        keep = (_host(roots["flag"]) == 1) & (st == 0) & (st2 == 0)
+    out = {}
+    for label in sorted(set(zip(nv[keep].tolist(), nf[keep].tolist()))):
+        sel = np.nonzero(keep & (nv == label[0]) & (nf == label[1]))[0]
+        sel = sel[np.lexsort((w[sel], k[sel]))]
+        out[label] = (w[sel], k[sel], cg[sel])
+    return out
+
+
+def hermite_branch(ks, omegas, cg):
+    """omega(k) of one branch as the piecewise-cubic Hermite interpolant through the roots (ks strictly increasing) with
+    the slopes cg = d omega / dk (ShootProblem.group_velocity): what a degree-6 fit_branch stands in for when the slopes are
+    not known.  Returns f(k, nu=0): omega (nu = 0) or d omega / dk (nu = 1) at scalar or array k; outside [ks[0], ks[-1]]
+    the cubic of the end interval is continued."""
+    x, y, d = (np.asarray(a, dtype=np.float64) for a in (ks, omegas, cg))
+    if not (x.ndim == 1 and x.shape == y.shape == d.shape and len(x) >= 2):
+        raise ValueError("ks, omegas, cg must be 1-D arrays of one length >= 2")
+    if not np.all(np.diff(x) > 0):
+        raise ValueError("ks must be strictly increasing")
+    h = np.diff(x)
+
+    def f(k, nu=0):
+        k = np.asarray(k, dtype=np.float64)
+        j = np.clip(np.searchsorted(x, k, side="right") - 1, 0, len(x) - 2)
+        hj = h[j]
+        t = (k - x[j]) / hj
+        if nu == 0:
+            return ((2 * t ** 3 - 3 * t ** 2 + 1) * y[j] + (t ** 3 - 2 * t ** 2 + t) * hj * d[j]
+                    + (-2 * t ** 3 + 3 * t ** 2) * y[j + 1] + (t ** 3 - t ** 2) * hj * d[j + 1])
+        if nu == 1:
+            return ((6 * t ** 2 - 6 * t) * (y[j] - y[j + 1]) / hj + (3 * t ** 2 - 4 * t + 1) * d[j]
+                    + (3 * t ** 2 - 2 * t) * d[j + 1])
+        raise ValueError("nu must be 0 or 1")
+    return f
+
+
 def write_vtk(dump_file, x, y, z, variables, names):
     """Legacy-VTK structured-grid dump of scalar fields on an irregular grid, byte for byte what the reference's
     `makeDumpVTK(x, y, z, variables, varList, dumpFile)` writes (Cylinder/Non-uniform density/Coronal/Movies/

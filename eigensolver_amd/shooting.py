@@ -38,6 +38,28 @@ class ModeSignature(NamedTuple):
     status: object            # uint8: PT_* of the exterior
 
 
+class RootSlopes(NamedTuple):
+    """es_shoot_root_slopes: the two sides of the matching condition with their exact partial derivatives, CUDA tensors.
+    outer, inner are [3, n] (value, d/d omega, d/dk); d, d_w, d_k [n] are D = outer - inner and its derivatives.  A pair
+    that is not PT_OK, or whose outputs are not finite, carries NaN throughout."""
+    outer: object
+    inner: object
+    d: object
+    d_w: object
+    d_k: object
+    status: object            # uint8: PT_* of the exterior
+
+    @property
+    def group_velocity(self):
+        """d omega / dk along the branch through each pair: -D_k / D_w."""
+        return -self.d_k / self.d_w
+
+    @property
+    def newton_dw(self):
+        """The Newton correction -D / D_w: how far in omega each pair lies from the root of its row."""
+        return -self.d / self.d_w
+
+
 def read_screen_counts(counts, capacity):
     """Read the four count words once (a CUDA tensor: this is the host synchronisation the async calls leave to the
     caller; a CPU tensor works the same).  Raises EsError, naming the failure of the synchronous call's
@@ -485,6 +507,31 @@ class ShootProblem:
         the launch is sized for the capacity and takes the count on the device)."""
         t = roots[0] if isinstance(roots, tuple) else roots
         return self.mode_signature(t["k"], t["w"], count=count)
+
+    def root_slopes(self, k, w, count=None):
+        """es_shoot_root_slopes at the (k, omega) pairs: the determinant of eval_points with its exact derivatives in omega
+        and k (a tangent-linear march, no difference step) -> RootSlopes.  count as in mode_signature: entries past
+        min(count, n) are left as allocated.  Nothing is read back."""
+        import torch
+        dk, dw = self._dev(k).reshape(-1), self._dev(w).reshape(-1)
+        n = dk.numel()
+        assert dw.numel() == n
+        if count is not None:
+            assert count.is_cuda and count.numel() >= 1 and count.dtype == torch.int32
+        outer = torch.empty((3, n), dtype=torch.float64, device=dk.device)
+        inner = torch.empty((3, n), dtype=torch.float64, device=dk.device)
+        st = torch.empty(n, dtype=torch.uint8, device=dk.device)
+        rc = self.ctx.lib.es_shoot_root_slopes(self.ctx.handle, self.handle, _lib.ptr(dk), _lib.ptr(dw), n,
+                                               _lib.ptr(count) if count is not None else None, _lib.ptr(outer),
+                                               _lib.ptr(inner), _lib.ptr(st))
+        _lib.check(self.ctx.handle, rc)
+        diff = outer - inner
+        return RootSlopes(outer, inner, diff[0], diff[1], diff[2], st)
+
+    def group_velocity(self, roots, count=None):
+        """d omega / dk of every entry of a root table (the forms label_roots takes): -D_k / D_w, a CUDA tensor."""
+        t = roots[0] if isinstance(roots, tuple) else roots
+        return self.root_slopes(t["k"], t["w"], count=count).group_velocity
 
     def _require_positive_cylinder(self):
         if not isinstance(self.eq, eqm._CylinderBase):

@@ -848,6 +848,39 @@ int es_shoot_mode_signature(es_context* ctx, const es_problem* prob, const doubl
                             int32_t* d_peak_node_value, int32_t* d_peak_node_flux,
                             double* d_peak_value, double* d_peak_flux, uint8_t* d_status);
 
+/* ======================================================================================================
+ * (11) Dispersion slopes of a root: the exact partial derivatives of the boundary determinant.  With D(k, omega) the
+ *     determinant es_shoot_eval_points returns, D_w = dD/d omega and D_k = dD/dk give at a root
+ *       the group speed            c_g = d omega / dk = -D_k / D_w,
+ *       the Newton correction      d omega = -D / D_w   (the acceptance residual as an error bar in omega),
+ *       D_w itself, the weight of the mode in an initial-value problem.
+ *     The reference's analysis scripts fit polynomials through hand-cut branches for this (np.polyfit, e.g.
+ *       Cylinder/Non-uniform flow/Coronal/Eigenfunctions/analysis_cylinder_flow_coronal.py);
+ *     difference quotients of section 2 need a step, and no fixed step is right both at a regular root and at a root beside
+ *     a pole of the exterior term.
+ *
+ *     es_shoot_root_slopes: one (k, omega) pair per lane; the adjoint march, the closed-form exterior and the boundary
+ *     algebra of es_shoot_eval_points carried in 3-component jets (value, d/d omega, d/dk) -- a tangent-linear evaluation,
+ *     exact to rounding, no step to choose.
+ *       d_outer / d_inner [3][n]: row 0 the value, row 1 d/d omega, row 2 d/dk of the two sides of the matching condition
+ *         (cylinders: xi_e and xi_i at the boundary; slabs: the total pressure outside and inside).  D = outer - inner is
+ *         the D of es_shoot_eval_points (same march; the reciprocals are grouped per RK4 step), D_w and D_k are the
+ *         differences of rows 1 and 2.  The rows are n apart, n the argument, whatever d_count holds.
+ *       d_status [n]: ES_PT_* of the exterior as in sections 5 and 10 (ES_PT_OK, ES_PT_LEAKY, ES_PT_NONFINITE;
+ *         ES_PT_CONTINUUM is not looked at).  A pair whose exterior is not ES_PT_OK, or one of whose six outputs is not
+ *         finite, gets NaN in all six; the other pairs do not depend on it.
+ *     Any of the three output pointers may be NULL: that output is skipped.
+ *     d_count (may be NULL): as in section 10 -- the device count word of an _async search; the kernel uses
+ *     min(max(*d_count, 0), n) and leaves entries beyond it alone.
+ *     Asynchronous on the context's stream, no host synchronisation.  n == 0 succeeds and touches nothing (the arrays may
+ *     then be NULL).  ES_ERR_INVALID_ARG: n < 0, a null problem, d_k or d_w null with n > 0; ES_ERR_UNSUPPORTED: an unknown
+ *     family.  Not offered: complex frequencies (section 6) and the closed-form uniform cylinder (section 4).
+ * ====================================================================================================== */
+int es_shoot_root_slopes(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w, int n,
+                         const int32_t* d_count /* may be NULL */,
+                         double* d_outer /* [3][n]: value, d/dw, d/dk */, double* d_inner /* [3][n] */,
+                         uint8_t* d_status);
+
 #ifdef __cplusplus
 }
 #endif
