@@ -223,11 +223,8 @@ __global__ __launch_bounds__(256) void audit_emit_kernel(const double* __restric
                                                          const int* __restrict__ block_off, int capacity,
                                                          int64_t* __restrict__ d_cell, uint8_t* __restrict__ d_kind) {
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= cells) return;
-  const uint64_t m = masks[c >> 6];
-  if (!((m >> (c & 63)) & 1ull)) return;
-  const int pos = es_cell_rank(masks, block_off, c);
-  if (pos >= capacity) return;
+  const int pos = es_flagged_pos(masks, block_off, c, cells, capacity);
+  if (pos < 0) return;
   const audit_point p = audit_load(D_scr, st_scr, D64, st64, c);
   const long row = c / nw;
   const bool inner = (int)(c - row * nw) < nw - 1;               // then c + 1 is a cell of the same row

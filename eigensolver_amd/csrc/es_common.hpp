@@ -83,8 +83,38 @@ int es_scan_block_counts_async(es_context* ctx, int nblocks);
 
 // The count convention of every kernel that takes (d_n, n_max): the launch is sized for n_max; the count is *d_n, read from
 // device memory and capped at n_max, or n_max itself when d_n == nullptr (the host knows the count).
+// d_n is a count that a stage of this library wrote: it is never negative, so only the cap is applied.
 __device__ __forceinline__ int es_count(const int* d_n, int n_max) {
   return d_n ? (*d_n < n_max ? *d_n : n_max) : n_max;
+}
+
+// The same convention for the entry points that take the count word of an _async search straight from the caller (branch
+// labels, root slopes): min(max(*d_count, 0), n), so a word the caller never had a search fill in cannot index backwards.
+__device__ __forceinline__ int es_count_clamped(const int32_t* d_count, int n) {
+  if (!d_count) return n;
+  const int c = *d_count;
+  return c < n ? (c < 0 ? 0 : c) : n;
+}
+
+// Ordered compaction of flagged slots, device side.  The format: bit l of masks[s / 64] is the flag of slot s = 64 (s / 64) + l
+// and block_counts[s / 256] counts the flags of a block of 256 slots (after the scan: the flags in front of the block).
+// es_flag_block writes it, es_cell_rank and es_flagged_pos read it.
+
+// Producer: called by all 256 threads of a flag workgroup (it has a barrier), thread t with the flag of slot
+// `slot` = 256 blockIdx.x + t.  Returns the number of flags of the block to thread 0 (0 to every other thread).
+__device__ __forceinline__ int es_flag_block(bool flag, long slot, uint64_t* __restrict__ masks,
+                                             int* __restrict__ block_counts) {
+  __shared__ int wave_cnt[4];
+  const uint64_t m = __ballot(flag);
+  if ((threadIdx.x & 63) == 0) {
+    masks[slot >> 6] = m;
+    wave_cnt[threadIdx.x >> 6] = __popcll(m);
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return 0;
+  const int total = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  block_counts[blockIdx.x] = total;
+  return total;
 }
 
 // Position of a flagged cell inside the ordered output, from the masks and the scanned block offsets.
@@ -99,4 +129,14 @@ __device__ __forceinline__ int es_cell_rank(const uint64_t* __restrict__ masks, 
   const uint64_t lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   pos += __popcll(m[wave_in_blk] & lower);
   return pos;
+}
+
+// Consumer guard of an emit / gather kernel: the position of slot `slot` in the ordered output, or -1 for a slot that is
+// out of range (>= n_slots), not flagged, or at or beyond the capacity of the output.
+__device__ __forceinline__ int es_flagged_pos(const uint64_t* __restrict__ masks, const int* __restrict__ block_off,
+                                              long slot, long n_slots, int capacity) {
+  if (slot >= n_slots) return -1;
+  if (!((masks[slot >> 6] >> (slot & 63)) & 1ull)) return -1;
+  const int pos = es_cell_rank(masks, block_off, slot);
+  return pos < capacity ? pos : -1;
 }

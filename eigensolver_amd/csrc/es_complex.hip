@@ -354,9 +354,7 @@ __device__ __forceinline__ int quarter_turns(int qa, int qb) {
 __global__ __launch_bounds__(256) void cx_flag_kernel(const double* __restrict__ Dre, const double* __restrict__ Dim,
                                                       const uint8_t* __restrict__ st, int n_re, int n_im, long cells,
                                                       uint64_t* __restrict__ masks, int* __restrict__ block_counts) {
-  __shared__ int wave_cnt[4];
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   bool flag = false;
   if (c < cells) {
     const long per_row = (long)n_re * n_im;
@@ -374,13 +372,7 @@ __global__ __launch_bounds__(256) void cx_flag_kernel(const double* __restrict__
       }
     }
   }
-  const uint64_t m = __ballot(flag);
-  if (lane == 0) {
-    masks[c >> 6] = m;
-    wave_cnt[threadIdx.x >> 6] = __popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  es_flag_block(flag, c, masks, block_counts);
 }
 
 __global__ __launch_bounds__(256) void cx_emit_kernel(const double* __restrict__ kv, const double* __restrict__ wre,
@@ -389,10 +381,8 @@ __global__ __launch_bounds__(256) void cx_emit_kernel(const double* __restrict__
                                                       const int* __restrict__ block_off, es_complex_root_table tab,
                                                       double* __restrict__ half_re, double* __restrict__ half_im) {
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= cells) return;
-  if (!((masks[c >> 6] >> (c & 63)) & 1ull)) return;
-  const int pos = es_cell_rank(masks, block_off, c);
-  if (pos >= tab.capacity) return;
+  const int pos = es_flagged_pos(masks, block_off, c, cells, tab.capacity);
+  if (pos < 0) return;
   const long per_row = (long)n_re * n_im;
   const long row = c / per_row;
   const long r = c - row * per_row;

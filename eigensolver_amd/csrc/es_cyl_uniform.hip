@@ -123,12 +123,11 @@ struct UniGrid {
 __global__ __launch_bounds__(256) void cyl_uniform_flag_kernel(ShootDev P, UniDev U, UniGrid G, double* __restrict__ Dout,
                                                                uint8_t* __restrict__ stout, uint64_t* __restrict__ masks,
                                                                int* __restrict__ block_counts) {
-  __shared__ int wave_cnt[4];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const long tile = (long)blockIdx.x * 4 + wave;                       // wave-uniform
   const long row = tile / G.tiles_per_row;
-  uint64_t mask = 0;
+  bool flag = false;
   if (row < G.rows) {
     const int t = (int)(tile - row * G.tiles_per_row);
     const int io = (int)(row / G.nk), ik = (int)(row - (long)io * G.nk);
@@ -143,8 +142,7 @@ __global__ __launch_bounds__(256) void cyl_uniform_flag_kernel(ShootDev P, UniDe
     const double d1 = __shfl_down(D, 1);
     const int ok1 = __shfl_down(ok0, 1);
     // lane 63 owns no cell; the last point of a row has no upper neighbour (ok1 = 0 there: j + 1 >= nw)
-    const bool flag = lane < UNI_TILE && ok0 && ok1 && (D * d1 < 0.0);
-    mask = __ballot(flag);
+    flag = lane < UNI_TILE && ok0 && ok1 && (D * d1 < 0.0);
     // lane 63's point is stored by the next tile, which has it as lane 0 -- unless this is the last tile of the row
     if (in && (lane < UNI_TILE || t == G.tiles_per_row - 1)) {
       const size_t o = (size_t)row * G.nw + j;
@@ -152,12 +150,7 @@ __global__ __launch_bounds__(256) void cyl_uniform_flag_kernel(ShootDev P, UniDe
       if (stout) stout[o] = st;
     }
   }
-  if (lane == 0) {
-    masks[tile] = mask;
-    wave_cnt[wave] = __popcll(mask);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  es_flag_block(flag, 64 * tile + lane, masks, block_counts);         // slot of this lane: masks[tile]
 }
 
 // record `pos` of the table = the pos-th flagged slot: k, row, order and the two grid frequencies of the cell
@@ -167,9 +160,8 @@ __global__ __launch_bounds__(256) void cyl_uniform_emit_kernel(UniGrid G, const 
   const long s = (long)blockIdx.x * 256 + threadIdx.x;
   const long tile = s >> 6;
   const int lane = (int)(s & 63);
-  if (!((masks[tile] >> lane) & 1ull)) return;
-  const int pos = es_cell_rank(masks, block_off, s);
-  if (pos >= tab.capacity) return;
+  const int pos = es_flagged_pos(masks, block_off, s, 64 * G.rows * G.tiles_per_row, tab.capacity);
+  if (pos < 0) return;
   const long row = tile / G.tiles_per_row;
   const int t = (int)(tile - row * G.tiles_per_row);
   const int io = (int)(row / G.nk), ik = (int)(row - (long)io * G.nk);

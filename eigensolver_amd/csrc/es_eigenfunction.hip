@@ -1,17 +1,9 @@
 // Eigenfunctions at given (k, omega): what the reference's analysis scripts recompute at a chosen root
-// (analysis_cylinder_flow_coronal.py:813-924).  One (k, omega) pair per lane for the interior, two RK4 marches each;
+// (analysis_cylinder_flow_coronal.py:813-924).  One (k, omega) pair per lane for the interior, the two RK4 marches of
+// interior_rows (es_interior_march.hpp, which says why the cylinder marches run outwards) with every node written;
 // one (pair, exterior point) per lane for the closed-form exterior.
-//   slabs      adjoint march to get the boundary flux from the far-end condition, then a forward march from x = -1 that
-//              writes the state at every node;
-//   cylinders  both marches run from the axis point OUT to the boundary.  Towards the axis the singular solution grows
-//              like r^-m in P and r^-(m+1) in xi_r (1e9 and 1e12 over the interval for m = 3), and a march in that direction
-//              amplifies its own rounding and truncation error by as much: xi_r near the axis came out wrong by a sixth of
-//              its maximum for m = 3.  Outwards the singular part decays.  The first march carries
-//              the two columns e = (1, 0) and d of the axis state to the boundary (d = (0, 1) for the kink conditions
-//              P(r_ax) = target, d = (a12, -a11) with target = 0 for the sausage condition P'(r_ax) = 0), beta follows
-//              from P(r_b) = P_b, and the second march writes target e + beta d at every node.
 // A pair whose exterior is not ES_PT_OK (leaky, non-finite) gets NaN in all four of its value / flux rows.
-#include "es_shoot_shared.hpp"
+#include "es_interior_march.hpp"
 
 namespace {
 using namespace es_shoot_shared;
@@ -20,126 +12,20 @@ template <int FAM>
 __global__ __launch_bounds__(64) void eigen_interior_kernel(ShootDev P, const double* __restrict__ kv,
                                                             const double* __restrict__ wv, int n,
                                                             double* __restrict__ val, double* __restrict__ flux) {
-  constexpr int NE = FamTraits<FAM>::NE;
-  constexpr int NB = FamTraits<FAM>::NB;
-  constexpr bool DIAG = FamTraits<FAM>::DIAG;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;
   const double k = in ? kv[i] : 1.0;
   const double w = in ? wv[i] : 1.0;
-  const KScal s = make_kscal(P, k);
-  const int nsteps = P.n_nodes - 1;
-  const double h = P.h, h2 = 0.5 * P.h, h6 = P.h / 6.0, h3 = P.h / 3.0;
-  SignTrack trk;
-  double b[NB], e[NE], e2[NE];
   const ExteriorLite X = exterior_lite(P, k, w, w);
   const bool ok = X.status == ES_PT_OK;
-  constexpr bool CYL = (FAM == FAM_CYL0 || FAM == FAM_CYLT);
-  double u, v, flux_scale = 1.0;     // flux = v * flux_scale (density slab) ; see store
-  auto store = [&](int node, const double* en) {
+  interior_rows<FAM>(P, k, w, X, [&](int node, double value, double f) {
     if (!in) return;
     const size_t o = (size_t)i * P.n_nodes + node;
-    if (!ok) { val[o] = NAN; flux[o] = NAN; return; }
-    val[o] = u;
-    if (CYL) {
-      const double x = P.xb + (double)node * P.h;
-      flux[o] = v / x;                                            // xi_r = Xi / r
-    } else if (FAM == FAM_SLABD) {
-      flux[o] = v * flux_scale;
-    } else {
-      const double Om = w - en[0];
-      const double Om2 = Om * Om;
-      flux[o] = P.rho_i * P.S_i * (s.kcT2 - Om2) / (Om * (s.kc2 - Om2)) * v;    // P_Ti(x) Vx', SF-G:433
-    }
-  };
-  if (CYL) {
-    // axis node: coefficient set and the two columns of the axis state
-    load_base<FAM>(P, 2 * nsteps, b);
-    make_entry<FAM>(b, s, e);
-    Coef Aax;
-    coefficients<FAM>(e, P, s, w, Aax, trk);
-    double target = 0.0, d0 = 0.0, d1 = 1.0;
-    if (P.axis_bc == ES_AXIS_KINK) target = P.bc_const_raw * X.outer;                  // P(r_ax) = c xi_e, CF:795
-    else if (P.axis_bc == ES_AXIS_ROTATION_KINK) target = -(P.bc_const_raw * X.outer);  // CR-KF:695-698
-    else { d0 = Aax.a12; d1 = -Aax.a11; }                                              // P'(r_ax) = 0, CD-C:1082-1085
-    // (1) columns e = (1, 0) and d to the boundary: steps of -h over the same node and mid-point entries
-    double p1 = 1.0, x1 = 0.0, p2 = d0, x2 = d1;
-    Coef A0 = Aax;
-    for (int j = nsteps - 1; j >= 0; --j) {
-      Coef Am, A1;
-      load_base<FAM>(P, 2 * j + 1, b);
-      make_entry<FAM>(b, s, e);
-      load_base<FAM>(P, 2 * j, b);
-      make_entry<FAM>(b, s, e2);
-      coefficients2<FAM>(e, e2, P, s, w, Am, A1, trk);
-      rk4_step_forward<DIAG>(p1, x1, A0, Am, A1, -h, -h2, -h6, -h3);
-      rk4_step_forward<DIAG>(p2, x2, A0, Am, A1, -h, -h2, -h6, -h3);
-      A0 = A1;
-    }
-    const double beta = (X.yb - target * p1) / p2;                                     // P(r_b) = P_b
-    // (2) the axis state marched out again, writing every node
-    u = target + beta * d0;
-    v = beta * d1;
-    A0 = Aax;
-    store(nsteps, e);
-    for (int j = nsteps - 1; j >= 0; --j) {
-      Coef Am, A1;
-      load_base<FAM>(P, 2 * j + 1, b);
-      make_entry<FAM>(b, s, e);
-      load_base<FAM>(P, 2 * j, b);
-      make_entry<FAM>(b, s, e2);
-      coefficients2<FAM>(e, e2, P, s, w, Am, A1, trk);
-      rk4_step_forward<DIAG>(u, v, A0, Am, A1, -h, -h2, -h6, -h3);
-      A0 = A1;
-      store(j, e2);
-    }
-    return;
-  }
-  // (1) adjoint march: the row of the transfer matrix picked by the far-end condition -> boundary state (u_b, v_b)
-  load_base<FAM>(P, 2 * nsteps, b);
-  make_entry<FAM, fam_scaled<FAM>()>(b, s, e);
-  Coef B0;
-  coefficients<FAM>(e, P, s, w, B0, trk);
-  double zp, zq;
-  adjoint_start(P, B0, zp, zq);
-  for (int j = nsteps - 1; j >= 0; --j) {
-    Coef Bm, B1;
-    load_base<FAM>(P, 2 * j + 1, b);
-    make_entry<FAM, fam_scaled<FAM>()>(b, s, e);
-    load_base<FAM>(P, 2 * j, b);
-    make_entry<FAM, fam_scaled<FAM>()>(b, s, e2);
-    coefficients2<FAM>(e, e2, P, s, w, Bm, B1, trk);
-    adjoint_step_normalised<FAM>(zp, zq, B0, Bm, B1, h, h2, h6, h3);      // z at its true scale
-    B0 = B1;
-  }
-  // boundary state from the same algebra as the determinant
-  if (FAM == FAM_SLABD) {
-    u = X.yb;
-    v = (P.slab_sign - zp) * u / zq;         // v = F Vx' ; P_T = v / w
-    flux_scale = 1.0 / w;
-  } else {
-    const double Omb = w - e2[0];
-    u = X.yb * Omb / X.Oe;
-    v = (P.slab_sign - zp) * u / zq;         // v = Vx' ; P_T = P_Ti(x) v
-  }
-  // (2) forward march from the boundary, writing every node
-  load_base<FAM>(P, 0, b);
-  make_entry<FAM>(b, s, e);
-  Coef A0;
-  coefficients<FAM>(e, P, s, w, A0, trk);
-  store(0, e);
-  for (int j = 0; j < nsteps; ++j) {
-    Coef Am, A1;
-    load_base<FAM>(P, 2 * j + 1, b);
-    make_entry<FAM>(b, s, e);
-    load_base<FAM>(P, 2 * j + 2, b);
-    make_entry<FAM>(b, s, e2);
-    coefficients2<FAM>(e, e2, P, s, w, Am, A1, trk);
-    rk4_step_forward<DIAG>(u, v, A0, Am, A1, h, h2, h6, h3);
-    A0 = A1;
-    store(j + 1, e2);
-  }
+    val[o] = ok ? value : NAN;
+    flux[o] = ok ? f : NAN;
+  });
 }
+
 
 // exterior: cylinders P = a I_m + b K_m, slabs Vx = a e^{mu x} + b e^{-mu x}; relative to the boundary value (+-1)
 __global__ __launch_bounds__(256) void eigen_exterior_kernel(ShootDev P, const double* __restrict__ kv,
@@ -211,6 +97,13 @@ int launch_interior(es_context* ctx, const es_problem* prob, const double* d_k, 
   return ES_SUCCESS;
 }
 
+int dispatch_interior(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w, int n, double* v,
+                      double* f) {
+#define CALL_INTERIOR(F) launch_interior<F>(ctx, prob, d_k, d_w, n, v, f)
+  ES_DISPATCH_FAMILY(prob->dev.family, CALL_INTERIOR)
+#undef CALL_INTERIOR
+}
+
 }  // namespace
 
 extern "C" int es_shoot_eigenfunction(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w,
@@ -224,14 +117,7 @@ extern "C" int es_shoot_eigenfunction(es_context* ctx, const es_problem* prob, c
   ES_REQUIRE(ctx, d_k && d_w && d_int_value && d_int_flux, "null pointer");
   ES_REQUIRE(ctx, n_ext == 0 || (d_ext_x && d_ext_value && d_ext_flux), "null exterior arrays");
   ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  switch (prob->dev.family) {
-    case FAM_CYL0: rc = launch_interior<FAM_CYL0>(ctx, prob, d_k, d_w, n, d_int_value, d_int_flux); break;
-    case FAM_CYLT: rc = launch_interior<FAM_CYLT>(ctx, prob, d_k, d_w, n, d_int_value, d_int_flux); break;
-    case FAM_SLABD: rc = launch_interior<FAM_SLABD>(ctx, prob, d_k, d_w, n, d_int_value, d_int_flux); break;
-    case FAM_SLABF: rc = launch_interior<FAM_SLABF>(ctx, prob, d_k, d_w, n, d_int_value, d_int_flux); break;
-    default: rc = ES_ERR_UNSUPPORTED;
-  }
+  const int rc = dispatch_interior(ctx, prob, d_k, d_w, n, d_int_value, d_int_flux);
   if (rc) return rc;
   if (n_ext > 0) {
     const long tot = (long)n * n_ext;

@@ -191,7 +191,6 @@ __global__ __launch_bounds__(256) void bracket_flag_kernel(const double* __restr
                                                            const uint8_t* __restrict__ st, int nw, long cells,
                                                            uint64_t* __restrict__ masks,
                                                            int* __restrict__ block_counts) {
-  __shared__ int wave_cnt[4];
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
   double d0 = 0.0; int ok0 = 0;
@@ -208,13 +207,7 @@ __global__ __launch_bounds__(256) void bracket_flag_kernel(const double* __restr
     const int j = (int)(c - row * nw);
     flag = (j < nw - 1) && ok0 && ok1 && (d0 * d1 < 0.0);
   }
-  const uint64_t m = __ballot(flag);
-  if (lane == 0) {
-    masks[c >> 6] = m;
-    wave_cnt[threadIdx.x >> 6] = __popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  es_flag_block(flag, c, masks, block_counts);
 }
 
 __global__ __launch_bounds__(256) void bracket_emit_kernel(const double* __restrict__ kv,
@@ -224,11 +217,8 @@ __global__ __launch_bounds__(256) void bracket_emit_kernel(const double* __restr
                                                            const int* __restrict__ block_off, es_root_table tab,
                                                            double* __restrict__ d_lo_sign, double* __restrict__ d_hi_sign) {
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= cells) return;
-  const uint64_t m = masks[c >> 6];
-  if (!((m >> (c & 63)) & 1ull)) return;
-  const int pos = es_cell_rank(masks, block_off, c);
-  if (pos >= tab.capacity) return;
+  const int pos = es_flagged_pos(masks, block_off, c, cells, tab.capacity);
+  if (pos < 0) return;
   const long row = c / nw;
   const int j = (int)(c - row * nw);
   const double k = kv[row];
@@ -487,21 +477,11 @@ void refine_superlinear_kernel(ShootDev P, es_root_table tab, const double* d_lo
 __global__ __launch_bounds__(256) void hybrid_flag_kernel(const int* __restrict__ info, const int* __restrict__ d_n,
                                                           int n_max, uint64_t* __restrict__ masks,
                                                           int* __restrict__ block_counts, unsigned long long* stats) {
-  __shared__ int wave_cnt[4];
   const int n = es_count(d_n, n_max);
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   const bool flag = i < n && (info[i] >> 2) != HYB_KEPT;
-  const uint64_t m = __ballot(flag);
-  if ((threadIdx.x & 63) == 0) {
-    masks[i >> 6] = m;
-    wave_cnt[threadIdx.x >> 6] = __popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int c = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-    block_counts[blockIdx.x] = c;
-    if (c) atomicAdd(stats + 2, (unsigned long long)c);
-  }
+  const int c = es_flag_block(flag, (long)i, masks, block_counts);                        // the block's total, to thread 0
+  if (c) atomicAdd(stats + 2, (unsigned long long)c);
 }
 
 // row `pos` of the fallback table = bracket idx[pos] with the state the section rounds left in its row
@@ -511,10 +491,8 @@ __global__ __launch_bounds__(256) void hybrid_gather_kernel(es_root_table tab, e
                                                             const int* __restrict__ d_n, int n_max) {
   const int n = es_count(d_n, n_max);
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
-  if (i >= n) return;
-  if (!((masks[i >> 6] >> (i & 63)) & 1ull)) return;
-  const int pos = es_cell_rank(masks, block_off, (long)i);
-  if (pos >= ftab.capacity) return;
+  const int pos = es_flagged_pos(masks, block_off, (long)i, (long)n, ftab.capacity);
+  if (pos < 0) return;
   ftab.d_k[pos] = tab.d_k[i];
   ftab.d_w_lo[pos] = tab.d_w_lo[i];
   ftab.d_w_hi[pos] = tab.d_w_hi[i];
@@ -1026,28 +1004,20 @@ void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, co
 // cells with the UNSURE bit -> ballot masks + block counts (same layout as bracket_flag_kernel)
 __global__ __launch_bounds__(256) void unsure_flag_kernel(const uint8_t* __restrict__ st, long cells,
                                                           uint64_t* __restrict__ masks, int* __restrict__ block_counts) {
-  __shared__ int wave_cnt[4];
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  const bool flag = (c < cells) && (st[c] & F32_UNSURE);
-  const uint64_t m = __ballot(flag);
-  if ((threadIdx.x & 63) == 0) {
-    masks[c >> 6] = m;
-    wave_cnt[threadIdx.x >> 6] = __popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  es_flag_block((c < cells) && (st[c] & F32_UNSURE), c, masks, block_counts);
 }
 
 // ordered list of the flagged cells: (k, omega) pairs for the fp64 point kernel and the cell index to scatter back to
 __global__ __launch_bounds__(256) void unsure_gather_kernel(const double* __restrict__ kv, const double* __restrict__ wv,
                                                             int nw, int w_mode, long cells,
                                                             const uint64_t* __restrict__ masks,
-                                                            const int* __restrict__ block_off, double* __restrict__ pk,
-                                                            double* __restrict__ pw, long* __restrict__ pcell) {
+                                                            const int* __restrict__ block_off, int capacity,
+                                                            double* __restrict__ pk, double* __restrict__ pw,
+                                                            long* __restrict__ pcell) {
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= cells) return;
-  if (!((masks[c >> 6] >> (c & 63)) & 1ull)) return;
-  const int pos = es_cell_rank(masks, block_off, c);
+  const int pos = es_flagged_pos(masks, block_off, c, cells, capacity);
+  if (pos < 0) return;
   const long row = c / nw;
   const int j = (int)(c - row * nw);
   const double k = kv[row];
@@ -1103,16 +1073,6 @@ int check_root_table(es_context* ctx, const es_root_table* table) {
              "null root table arrays");
   return ES_SUCCESS;
 }
-
-// `return CALL(FAM)` with the family of a problem as the template argument
-#define ES_DISPATCH_FAMILY(fam, CALL)                      \
-  switch (fam) {                                           \
-    case FAM_CYL0: return CALL(FAM_CYL0);                  \
-    case FAM_CYLT: return CALL(FAM_CYLT);                  \
-    case FAM_SLABD: return CALL(FAM_SLABD);                \
-    case FAM_SLABF: return CALL(FAM_SLABF);                \
-    default: return ES_ERR_UNSUPPORTED;                    \
-  }
 
 // Launch shape of the grid kernel = (PTS points per lane, WPE waves per SIMD the register cap allows).  Every shape runs
 // workgroups of at most 256 threads (one wave per SIMD of a CU) over tiles (k-row, omega-segment of T * PTS points) and
@@ -1696,23 +1656,24 @@ extern "C" int es_shoot_eval_grid_ex(es_context* ctx, const es_problem* prob, co
 #undef CALL_GRID
 }
 
+// what launch_grid<FAM> picks for a row of nw frequencies
+template <int FAM>
+static int grid_shape_of(const es_problem* prob, int nw, int* h_pts, int* h_wpe, int* h_track) {
+  const bool track = !(fam_has_bands<FAM>() && prob->dev.use_bands);
+  const GridShape g = pick_shape<FAM>(nw, track);
+  *h_pts = g.pts; *h_wpe = g.wpe; *h_track = track ? 1 : 0;
+  if (rows2_shape<FAM>(nw, track)) { *h_pts = -((nw + 127) / 128); *h_wpe = 3; }
+  return ES_SUCCESS;
+}
+
 extern "C" int es_shoot_grid_shape(es_context* ctx, const es_problem* prob, int nw, int* h_pts, int* h_wpe, int* h_track) {
   if (!ctx) return ES_ERR_INVALID_ARG;
   int rc = check_problem(ctx, prob);
   if (rc) return rc;
   ES_REQUIRE(ctx, h_pts && h_wpe && h_track && nw > 0, "shape query arguments");
-  GridShape g{0, 0};
-  bool track = true;
-  switch (prob->dev.family) {
-    case FAM_CYL0: track = !prob->dev.use_bands; g = pick_shape<FAM_CYL0>(nw, track); break;
-    case FAM_CYLT: g = pick_shape<FAM_CYLT>(nw, true); break;
-    case FAM_SLABD: track = !prob->dev.use_bands; g = pick_shape<FAM_SLABD>(nw, track); break;
-    case FAM_SLABF: track = !prob->dev.use_bands; g = pick_shape<FAM_SLABF>(nw, track); break;
-    default: return ES_ERR_UNSUPPORTED;
-  }
-  *h_pts = g.pts; *h_wpe = g.wpe; *h_track = track ? 1 : 0;
-  if (prob->dev.family != FAM_CYLT && rows2_shape<FAM_CYL0>(nw, track)) { *h_pts = -((nw + 127) / 128); *h_wpe = 3; }
-  return ES_SUCCESS;
+#define CALL_SHAPE(F) grid_shape_of<F>(prob, nw, h_pts, h_wpe, h_track)
+  ES_DISPATCH_FAMILY(prob->dev.family, CALL_SHAPE)
+#undef CALL_SHAPE
 }
 
 extern "C" int es_shoot_eval_grid(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
@@ -1995,7 +1956,7 @@ int screened_search(es_context* ctx, const es_problem* prob, const double* d_k, 
   // 2. gather them, re-evaluate in fp64, scatter back
   if (n_pts > 0) {
     hipLaunchKernelGGL(unsure_gather_kernel, grid_blocks, dim3(256), 0, ctx->stream, d_k, d_w, nw, w_mode, cells,
-                       ctx->d_masks, ctx->d_block_counts, pk, pw, pcell);
+                       ctx->d_masks, ctx->d_block_counts, es_bound(n_pts), pk, pw, pcell);
     ES_HIP_CHECK(ctx, hipGetLastError());
     rc = dispatch_points(ctx, prob, pk, pw, h ? nullptr : c + 1, n_pts, pD, nullptr, pst);
     if (rc) return rc;

@@ -9,6 +9,16 @@ struct es_problem {
   es_shoot_desc desc;
 };
 
+// `return CALL(FAM)` with the family of a problem as the template argument
+#define ES_DISPATCH_FAMILY(fam, CALL)                      \
+  switch (fam) {                                           \
+    case FAM_CYL0: return CALL(FAM_CYL0);                  \
+    case FAM_CYLT: return CALL(FAM_CYLT);                  \
+    case FAM_SLABD: return CALL(FAM_SLABD);                \
+    case FAM_SLABF: return CALL(FAM_SLABF);                \
+    default: return ES_ERR_UNSUPPORTED;                    \
+  }
+
 namespace es_shoot_shared {
 
 constexpr int ES_REFINE_POLISH = 2;   // regula-falsi steps after the 9-section rounds (0: report the bracket midpoint)
@@ -64,8 +74,7 @@ __device__ __forceinline__ void finish_point(const ShootDev& P, const Mismatch& 
   if (crossed) st = ES_PT_CONTINUUM;
 }
 
-// forward RK4 step of one state vector (u, v):  y' = A y  (the writing march of es_eigenfunction.hip, the reducing march of
-// es_signature.hip)
+// forward RK4 step of one state vector (u, v):  y' = A y  (interior_rows of es_interior_march.hpp)
 template <bool DIAG>
 __device__ __forceinline__ void rk4_step_forward(double& u, double& v, const Coef& A0, const Coef& Am, const Coef& A1,
                                                  double h, double h2, double h6, double h3) {

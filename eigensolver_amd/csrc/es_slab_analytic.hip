@@ -112,7 +112,6 @@ __global__ __launch_bounds__(256) void slab_scan_flag_kernel(SlabP p, const doub
                                                              const double* __restrict__ Wv, int nW, long cells,
                                                              double step, uint64_t* __restrict__ masks,
                                                              int* __restrict__ block_counts) {
-  __shared__ int wave_cnt[4];
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
   bool flag = false;
   if (c < cells) {
@@ -124,14 +123,7 @@ __global__ __launch_bounds__(256) void slab_scan_flag_kernel(SlabP p, const doub
     const double prod = disp_rel<MODE>(p, V1, K) * disp_rel<MODE>(p, V2, K);
     flag = prod < 0.0;            // NaN products compare false, as in the reference
   }
-  const uint64_t m = __ballot(flag);
-  const int wid = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    masks[c >> 6] = m;
-    wave_cnt[wid] = __popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  es_flag_block(flag, c, masks, block_counts);
 }
 
 __global__ __launch_bounds__(256) void slab_scan_emit_kernel(const double* __restrict__ Kv,
@@ -141,11 +133,8 @@ __global__ __launch_bounds__(256) void slab_scan_emit_kernel(const double* __res
                                                              double* __restrict__ rootK, double* __restrict__ rootW,
                                                              int capacity) {
   const long c = (long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= cells) return;
-  const uint64_t m = masks[c >> 6];
-  if (!((m >> (c & 63)) & 1ull)) return;
-  const int pos = es_cell_rank(masks, block_off, c);
-  if (pos >= capacity) return;
+  const int pos = es_flagged_pos(masks, block_off, c, cells, capacity);
+  if (pos < 0) return;
   const long iK = c / nW;
   const int iW = (int)(c - iK * nW);
   const double V1 = Wv[iW];

@@ -339,11 +339,7 @@ __global__ __launch_bounds__(64) void root_slopes_kernel(ShootDev P, const doubl
                                                          double* __restrict__ inner, uint8_t* __restrict__ status) {
   constexpr int NB = FamTraits<FAM>::NB;
   constexpr bool CYL = (FAM == FAM_CYL0 || FAM == FAM_CYLT);
-  int cnt = n;                                                 // n stays the row length of the [3][n] outputs
-  if (d_count) {                                               // the count of an _async search: min(max(*d_count, 0), n)
-    const int c = *d_count;
-    cnt = c < n ? (c < 0 ? 0 : c) : n;
-  }
+  const int cnt = es_count_clamped(d_count, n);                // n stays the row length of the [3][n] outputs
   if ((int)(blockIdx.x * blockDim.x) >= cnt) return;           // the whole wave lies past the count
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < cnt;
@@ -425,12 +421,6 @@ extern "C" int es_shoot_root_slopes(es_context* ctx, const es_problem* prob, con
   ES_REQUIRE(ctx, d_k && d_w, "null pointer");
   ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 #define ES_SLOPES(F) launch_slopes<F>(ctx, prob, d_k, d_w, n, d_count, d_outer, d_inner, d_status)
-  switch (prob->dev.family) {
-    case FAM_CYL0: return ES_SLOPES(FAM_CYL0);
-    case FAM_CYLT: return ES_SLOPES(FAM_CYLT);
-    case FAM_SLABD: return ES_SLOPES(FAM_SLABD);
-    case FAM_SLABF: return ES_SLOPES(FAM_SLABF);
-    default: return ES_ERR_UNSUPPORTED;
-  }
+  ES_DISPATCH_FAMILY(prob->dev.family, ES_SLOPES)
 #undef ES_SLOPES
 }

@@ -237,6 +237,12 @@ int launch_worker(es_context* ctx, const es_problem* prob, const WorkerArgs& a) 
   return ES_SUCCESS;
 }
 
+int dispatch_worker(es_context* ctx, const es_problem* prob, const WorkerArgs& a) {
+#define CALL_WORKER(F) launch_worker<F>(ctx, prob, a)
+  ES_DISPATCH_FAMILY(prob->dev.family, CALL_WORKER)
+#undef CALL_WORKER
+}
+
 }  // namespace
 
 extern "C" int es_worker_run(es_context* ctx, const es_problem* prob, const es_worker_spec* spec, const double* d_k,
@@ -280,14 +286,7 @@ extern "C" int es_worker_run(es_context* ctx, const es_problem* prob, const es_w
     if (const char* ev = getenv("ES_WORKER_EVAL_CAP")) { const long v = atol(ev); if (v > 0) a.eval_cap = v; }   // test aid
     a.abort_flag = ctx->d_total;
     if (hipMemsetAsync(ctx->d_total, 0, sizeof(int), ctx->stream) != hipSuccess) rc = ES_ERR_HIP;
-    if (rc == ES_SUCCESS)
-    switch (prob->dev.family) {
-      case FAM_CYL0: rc = launch_worker<FAM_CYL0>(ctx, prob, a); break;
-      case FAM_CYLT: rc = launch_worker<FAM_CYLT>(ctx, prob, a); break;
-      case FAM_SLABD: rc = launch_worker<FAM_SLABD>(ctx, prob, a); break;
-      case FAM_SLABF: rc = launch_worker<FAM_SLABF>(ctx, prob, a); break;
-      default: rc = ES_ERR_UNSUPPORTED;
-    }
+    if (rc == ES_SUCCESS) rc = dispatch_worker(ctx, prob, a);
   }
   if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == ES_SUCCESS) {
     ctx->last_error = "worker kernel failed";

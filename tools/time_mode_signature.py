@@ -17,6 +17,7 @@ Before timing, the labels of the signature leg are compared with those of the to
 median / min / max ms per leg over the repeats and the ratios is printed and appended to --out.
 
     python tools/time_mode_signature.py [--repeats 20] [--warmup 3] [--log2n 17] [--out profiles/mode_signature_timing.jsonl]
+                                        [--lib another/libeigensolver_amd.so]
 """
 import argparse
 import json
@@ -49,6 +50,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2n", type=int, default=17)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mode_signature_timing.jsonl"))
+    ap.add_argument("--lib", default=None, help="another build of the library to time (e.g. the parent commit's) instead "
+                                                "of eigensolver_amd/lib/libeigensolver_amd.so")
     a = ap.parse_args()
     assert a.repeats >= 10, "at least 10 timed repeats per leg"
     import numpy as np
@@ -58,7 +61,7 @@ def main():
     assert torch.cuda.is_available(), "this tool measures on the GPU; there is nothing to fall back to"
     dev = torch.device("cuda", torch.cuda.current_device())
     stream = torch.cuda.Stream(device=dev)
-    ctx = _lib.Context(dev.index or 0, stream=stream)
+    ctx = _lib.Context(dev.index or 0, stream=stream, lib=_lib.load_variant(a.lib) if a.lib else None)
     n = 1 << a.log2n
     with torch.cuda.stream(stream):
         gp = ShootProblem(bench.workload_equilibrium(), "kink", ctx=ctx)
@@ -119,7 +122,8 @@ def main():
             e1.synchronize()
             if it >= a.warmup:
                 ms[name].append(e0.elapsed_time(e1))
-    line = {"device": torch.cuda.get_device_name(dev), "pairs": n, "nodes": N, "distinct_roots": n_roots, "brackets": int(cnt),
+    line = {"device": torch.cuda.get_device_name(dev), "lib": os.path.basename(a.lib) if a.lib else "default",
+            "pairs": n, "nodes": N, "distinct_roots": n_roots, "brackets": int(cnt),
             "pairs_ok": int(ok.sum().item()), "labels": [list(x) for x in labels], "labels_differ_from_torch": differ,
             "repeats": a.repeats, "warmup": a.warmup, "legs": {}}
     for name, v in ms.items():
