@@ -317,4 +317,7 @@ def _sig(lib):
     lib.es_shoot_mode_signature.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
     # (11) dispersion slopes
     lib.es_shoot_root_slopes.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp]
+    # (12) slopes and Newton tracing of complex roots
+    lib.es_complex_root_slopes.argtypes = [vp, vp, i, vp, vp, vp, i, vp, vp, vp, vp]
+    lib.es_complex_newton.argtypes = [vp, vp, i, vp, vp, vp, i, vp, i, d, d, d, vp, vp, vp, vp, vp, vp]
     return lib

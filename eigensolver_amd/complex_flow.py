@@ -14,7 +14,9 @@ complex secant steps and accepted if 100 |D_c| / max(|outer|, |inner|) < tol.
 """
 import ctypes as C
 import math
+import sys
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -22,6 +24,30 @@ from . import _lib, equilibrium as eqm
 from .shooting import ShootProblem, W_ABSOLUTE, W_PHASE_SPEED
 
 CX_SFX, CX_SFG = 0, 1
+DBL_MAX = sys.float_info.max
+
+
+class ComplexRootSlopes(NamedTuple):
+    """es_complex_root_slopes: the two sides of the matching condition with their exact derivatives, complex128 CUDA tensors.
+    outer, inner are [3, n] (value, d/d omega, d/dk); d, d_w, d_k [n] are D_c = outer - inner and its derivatives.  A pair
+    that is not PT_OK, or whose outputs are not finite, carries NaN throughout."""
+    outer: object
+    inner: object
+    d: object
+    d_w: object
+    d_k: object
+    status: object            # uint8: the status of eval_points
+
+    @property
+    def group_velocity(self):
+        """d omega / dk along the branch through each pair, -D_k / D_w (complex): the real part is the group speed, the
+        imaginary part the slope of the growth rate."""
+        return -self.d_k / self.d_w
+
+    @property
+    def newton_dw(self):
+        """The Newton correction -D / D_w: how far in omega each pair lies from the root of its row."""
+        return -self.d / self.d_w
 
 
 @dataclass
@@ -167,6 +193,110 @@ class SlabComplexFlow:
         _lib.check(self.ctx.handle, rc)
         x_int = torch.linspace(p.desc.x_boundary, p.desc.x_end, N, dtype=torch.float64, device=dev)
         return dict(x_int=x_int, value_int=vi, flux_int=fi, x_ext=xe, value_ext=ve, flux_ext=fe, status=st)
+
+    # ---- slopes and Newton tracing (C ABI section 12) ------------------------------------------------------------------
+    def _pairs(self, mode, k, w):
+        """(problem, k, Re w, Im w) on the device, k broadcast against the complex w; tensors are taken as they are."""
+        import torch
+        p = self.problem(mode)
+        dev = f"cuda:{self.ctx.device}"
+        if isinstance(w, torch.Tensor):
+            w = w.to(device=dev, dtype=torch.complex128).reshape(-1)
+        else:
+            w = torch.as_tensor(np.asarray(w, dtype=complex).reshape(-1), device=dev)
+        dk = torch.broadcast_to(p._dev(k).reshape(-1), w.shape).contiguous()
+        return p, dk, w.real.contiguous(), w.imag.contiguous()
+
+    @staticmethod
+    def _count_ptr(count):
+        import torch
+        if count is None:
+            return None
+        assert count.is_cuda and count.numel() >= 1 and count.dtype == torch.int32
+        return _lib.ptr(count)
+
+    def root_slopes(self, mode, k, w, count=None):
+        """es_complex_root_slopes at the complex (k, omega) pairs: D_c of eval_points with its exact derivatives in omega
+        (holomorphic) and k, a tangent-linear march with no difference step -> ComplexRootSlopes.  k is broadcast against
+        w; both may be tensors.  count: an int32 CUDA tensor holding the number of valid pairs; entries past
+        min(count, n) are left as allocated.  Nothing is read back."""
+        import torch
+        p, dk, dre, dim = self._pairs(mode, k, w)
+        n, dev = dk.numel(), dk.device
+        outer = torch.empty((3, n), dtype=torch.complex128, device=dev)
+        inner = torch.empty((3, n), dtype=torch.complex128, device=dev)
+        st = torch.empty(n, dtype=torch.uint8, device=dev)
+        rc = self.ctx.lib.es_complex_root_slopes(self.ctx.handle, p.handle, self.variant, _lib.ptr(dk), _lib.ptr(dre),
+                                                 _lib.ptr(dim), n, self._count_ptr(count), _lib.ptr(outer),
+                                                 _lib.ptr(inner), _lib.ptr(st))
+        _lib.check(self.ctx.handle, rc)
+        diff = outer - inner
+        return ComplexRootSlopes(outer, inner, diff[0], diff[1], diff[2], st)
+
+    def group_velocity(self, mode, roots, count=None):
+        """d omega / dk (complex) of every entry of a find_roots table: -D_k / D_w, a CUDA tensor."""
+        t = roots[0] if isinstance(roots, tuple) else roots
+        return self.root_slopes(mode, t["k"], t["w"], count=count).group_velocity
+
+    def newton(self, mode, k, w0, max_iter=8, step_cap=None, max_shift=None, tol_percent=None, count=None):
+        """es_complex_newton from the guesses w0 at fixed k (broadcast against w0): dict of CUDA tensors w (complex128),
+        resid (percent), iters, flag (int32) and dwdk (complex128, -D_k / D_w at the final w).  step_cap caps the length
+        of a step, max_shift the distance |w - w0| an accepted root may have travelled (both default to no limit);
+        tol_percent defaults to P_TOL.  flag = 1: the iteration met no leaky or singular point, the final point is
+        ES_PT_OK, resid < tol_percent and |w - w0| <= max_shift.  Nothing is read back."""
+        import torch
+        p, dk, gre, gim = self._pairs(mode, k, w0)
+        n, dev = dk.numel(), dk.device
+        wre, wim, resid = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
+        dwdk = torch.empty(n, dtype=torch.complex128, device=dev)
+        iters, flag = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        rc = self.ctx.lib.es_complex_newton(self.ctx.handle, p.handle, self.variant, _lib.ptr(dk), _lib.ptr(gre), _lib.ptr(gim),
+                                            n, self._count_ptr(count), int(max_iter),
+                                            DBL_MAX if step_cap is None else min(float(step_cap), DBL_MAX),
+                                            DBL_MAX if max_shift is None else min(float(max_shift), DBL_MAX),
+                                            self.P_TOL if tol_percent is None else float(tol_percent), _lib.ptr(wre),
+                                            _lib.ptr(wim), _lib.ptr(resid), _lib.ptr(dwdk), _lib.ptr(iters), _lib.ptr(flag))
+        _lib.check(self.ctx.handle, rc)
+        return dict(w=torch.complex(wre, wim), resid=resid, iters=iters, flag=flag, dwdk=dwdk)
+
+    def densify(self, mode, k, w, k_fine, shift_factor=4.0, **newton_kw):
+        """One branch traced to the wavenumbers k_fine from a coarse scan: k strictly increasing with the roots w on it.
+        (1) root_slopes at the coarse roots, (2) the complex piecewise-cubic Hermite prediction at k_fine (the cubic of the
+        end interval continued outside [k[0], k[-1]]), formed on the device, (3) one newton call over all fine points.
+        Dict of CUDA tensors k, w, dwdk, resid, iters, flag, predicted and max_shift.  Nothing is read back.
+        max_shift: a number from the caller goes to newton as it is.  Left out, every fine point gets the bound of its
+        coarse interval [k_j, k_j+1], shift_factor (4) times the larger of the interval's two end-point Hermite defects
+            |w_j+1 - w_j - h s_j|,  |w_j+1 - w_j - h s_j+1|      (s = d omega / dk, h = k_j+1 - k_j)
+        -- how far the tangent from one end misses the root at the other, a scale for how far the curve bends inside the
+        interval and so for how far the cubic can lie from it -- and no less than 1e-8 max(1, |w_j|); newton then runs
+        without a limit and the flag is cleared, on the device, where |w - predicted| exceeds the bound."""
+        import torch
+        p, dk, dre, dim = self._pairs(mode, k, w)
+        wc = torch.complex(dre, dim)
+        if dk.numel() < 2:
+            raise ValueError("densify needs at least two coarse rows")
+        kf = p._dev(k_fine).reshape(-1)
+        s = self.root_slopes(mode, dk, wc).group_velocity
+        h = dk[1:] - dk[:-1]
+        j = torch.clamp(torch.searchsorted(dk, kf, right=True) - 1, 0, dk.numel() - 2)
+        hj = h[j]
+        t = (kf - dk[j]) / hj
+        t2, t3 = t * t, t * t * t
+        pred = ((2 * t3 - 3 * t2 + 1) * wc[j] + (t3 - 2 * t2 + t) * hj * s[j]
+                + (-2 * t3 + 3 * t2) * wc[j + 1] + (t3 - t2) * hj * s[j + 1])
+        given = newton_kw.get("max_shift") is not None
+        out = self.newton(mode, kf, pred, **newton_kw)
+        if given:
+            out["max_shift"] = torch.full_like(kf, float(newton_kw["max_shift"]))
+        else:
+            dw = wc[1:] - wc[:-1]
+            defect = torch.maximum((dw - h * s[:-1]).abs(), (dw - h * s[1:]).abs())
+            bound = torch.maximum(shift_factor * defect, 1e-8 * torch.clamp(wc[:-1].abs(), min=1.0))[j]
+            out["flag"] = torch.where((out["w"] - pred).abs() <= bound, out["flag"], torch.zeros_like(out["flag"]))
+            out["max_shift"] = bound
+        out["k"] = kf
+        out["predicted"] = pred
+        return out
 
     # ---- perturbation fields (C ABI section 9) -----------------------------------------------------------------------
     def polarisation(self, mode, k, w, n_ext=500, reference_quirks=True):

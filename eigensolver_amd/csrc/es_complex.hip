@@ -7,52 +7,13 @@
 // One (k, omega) point per lane.  The profile table (U, U', U'' at nodes and mid-points) is staged in LDS chunk by
 // chunk as in shoot_point; every lane forms its own complex coefficients.  This path is a handful of complex
 // divisions per node and is not on the benchmark path: written for clarity, IEEE divisions throughout.
-#include "es_shoot_shared.hpp"
+#include "es_complex_shared.hpp"
 
 namespace {
-using namespace es_shoot_shared;
-
-struct cx {
-  double re, im;
-};
-__device__ __forceinline__ cx mk(double a, double b = 0.0) { return cx{a, b}; }
-__device__ __forceinline__ cx operator+(cx a, cx b) { return cx{a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ cx operator-(cx a, cx b) { return cx{a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ cx operator-(cx a) { return cx{-a.re, -a.im}; }
-__device__ __forceinline__ cx operator*(cx a, cx b) { return cx{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ cx operator*(double s, cx a) { return cx{s * a.re, s * a.im}; }
-__device__ __forceinline__ cx operator/(cx a, cx b) {
-  const double n = b.re * b.re + b.im * b.im;
-  return cx{(a.re * b.re + a.im * b.im) / n, (a.im * b.re - a.re * b.im) / n};
-}
-__device__ __forceinline__ cx operator-(double s, cx a) { return cx{s - a.re, -a.im}; }
-__device__ __forceinline__ cx operator+(double s, cx a) { return cx{s + a.re, a.im}; }
-__device__ __forceinline__ double cabs2(cx a) { return a.re * a.re + a.im * a.im; }
-__device__ __forceinline__ double cabs_(cx a) { return hypot(a.re, a.im); }
-__device__ __forceinline__ bool cfinite(cx a) { return isfinite(a.re) && isfinite(a.im); }
-// principal square root (Re >= 0)
-__device__ __forceinline__ cx csqrt_(cx z) {
-  const double r = hypot(z.re, z.im);
-  if (r == 0.0) return cx{0.0, 0.0};
-  double a = sqrt(0.5 * (r + fabs(z.re)));
-  double b = 0.5 * z.im / a;
-  if (z.re >= 0.0) return cx{a, b};
-  return cx{fabs(b), copysign(a, z.im)};
-}
-__device__ __forceinline__ cx cexp_(cx z) {
-  const double e = exp(z.re);
-  double s, c;
-  sincos(z.im, &s, &c);
-  return cx{e * c, e * s};
-}
+using namespace es_complex_shared;
 
 // interior coefficients at one node: u' = v, v' = a21 u + a22 v  with  a21 = -coeff, a22 = -D
 struct CxCoef { cx a21, a22; };
-
-struct CxConsts {
-  double k, k2, kc2, kvA2, kcT2, k4c, S_i;
-  int variant;
-};
 
 __device__ __forceinline__ void cx_terms(const CxConsts& C, cx w, double U, double dU, cx& Om, cx& Om2, cx& m0, cx& D) {
   Om = w - mk(C.k * U);
@@ -79,15 +40,6 @@ __device__ __forceinline__ CxCoef cx_coef(const CxConsts& C, cx w, double U, dou
 __device__ __forceinline__ void cx_rhs(const CxCoef& A, cx p, cx q, cx& kp, cx& kq) {
   kp = A.a21 * q;
   kq = p + A.a22 * q;
-}
-
-__device__ __forceinline__ CxConsts cx_consts(const ShootDev& P, int variant, double k) {
-  CxConsts C;
-  C.k = k; C.k2 = k * k;
-  C.kc2 = C.k2 * P.c2_i; C.kvA2 = C.k2 * P.vA2_i; C.kcT2 = C.k2 * P.cT2_i;
-  C.k4c = C.k2 * C.k2 * P.cT2_i * P.c2_i;
-  C.S_i = P.S_i; C.variant = variant;
-  return C;
 }
 
 // exterior (closed form, decaying branch), SF-X:369-371, :419-426:  Vx_e ~ gp e^{mu (x + R)} + gm e^{-mu (x + R)}
@@ -431,16 +383,6 @@ __global__ __launch_bounds__(64) void cx_refine_kernel(ShootDev P, int variant, 
     tab.d_resid[i] = rel1;
     tab.d_flag[i] = (s1 == ES_PT_OK && rel1 < tol_percent && dist2 <= 4.0 * diag2) ? 1 : 0;
   }
-}
-
-int check_cx(es_context* ctx, const es_problem* prob, int variant) {
-  ES_REQUIRE(ctx, prob != nullptr, "null problem");
-  ES_REQUIRE(ctx, variant == ES_CX_SFX || variant == ES_CX_SFG, "variant");
-  if (prob->dev.family != FAM_SLABF) {
-    ctx->last_error = "complex frequencies are implemented for ES_GEOM_SLAB_FLOW problems only";
-    return ES_ERR_UNSUPPORTED;
-  }
-  return ES_SUCCESS;
 }
 
 }  // namespace

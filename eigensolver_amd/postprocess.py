@@ -133,6 +133,66 @@ def hermite_branch(ks, omegas, cg):
     return f
 
 
+def _hermite_complex_arrays(ks, omegas, dwdk):
+    x = np.asarray(ks, dtype=np.float64)
+    y, d = np.asarray(omegas, dtype=np.complex128), np.asarray(dwdk, dtype=np.complex128)
+    if not (x.ndim == 1 and x.shape == y.shape == d.shape and len(x) >= 2):
+        raise ValueError("ks, omegas, dwdk must be 1-D arrays of one length >= 2")
+    if not np.all(np.diff(x) > 0):
+        raise ValueError("ks must be strictly increasing")
+    return x, y, d
+
+
+def hermite_branch_complex(ks, omegas, dwdk):
+    """hermite_branch for a branch of complex roots (SlabComplexFlow.find_roots / densify): the piecewise-cubic Hermite
+    interpolant through the complex omegas (ks real, strictly increasing) with the complex slopes dwdk = d omega / dk
+    (SlabComplexFlow.group_velocity).  Returns f(k, nu=0): omega (nu = 0) or d omega / dk (nu = 1), complex, at scalar or
+    array k; outside [ks[0], ks[-1]] the cubic of the end interval is continued."""
+    x, y, d = _hermite_complex_arrays(ks, omegas, dwdk)
+    h = np.diff(x)
+
+    def f(k, nu=0):
+        k = np.asarray(k, dtype=np.float64)
+        j = np.clip(np.searchsorted(x, k, side="right") - 1, 0, len(x) - 2)
+        hj = h[j]
+        t = (k - x[j]) / hj
+        if nu == 0:
+            return ((2 * t ** 3 - 3 * t ** 2 + 1) * y[j] + (t ** 3 - 2 * t ** 2 + t) * hj * d[j]
+                    + (-2 * t ** 3 + 3 * t ** 2) * y[j + 1] + (t ** 3 - t ** 2) * hj * d[j + 1])
+        if nu == 1:
+            return ((6 * t ** 2 - 6 * t) * (y[j] - y[j + 1]) / hj + (3 * t ** 2 - 4 * t + 1) * d[j]
+                    + (3 * t ** 2 - 2 * t) * d[j + 1])
+        raise ValueError("nu must be 0 or 1")
+    return f
+
+
+def most_unstable(ks, omegas, dwdk):
+    """The growth-rate maxima of one branch of complex roots: in every interval of ks (strictly increasing) where
+    Im d omega / dk goes from positive to non-positive, the maximum of Im omega of that interval's Hermite cubic
+    (hermite_branch_complex), found in closed form as the root of the derivative quadratic at which the derivative falls.
+    Returns (k*, omega*): a float64 and a complex128 array with one entry per such interval, empty when there is none."""
+    x, y, d = _hermite_complex_arrays(ks, omegas, dwdk)
+    f = hermite_branch_complex(x, y, d)
+    k_out = []
+    for j in range(len(x) - 1):
+        d0, d1 = d[j].imag, d[j + 1].imag
+        if not (d0 > 0.0 and d1 <= 0.0):
+            continue
+        h, dy = x[j + 1] - x[j], y[j].imag - y[j + 1].imag
+        # h (Im omega)'(t) = A t^2 + B t + C on t in [0, 1]; C > 0 and A + B + C = h d1 <= 0: it falls through zero once
+        A, B, C = 6.0 * dy + 3.0 * h * (d0 + d1), -6.0 * dy - 4.0 * h * d0 - 2.0 * h * d1, h * d0
+        if A == 0.0:
+            cand = [-C / B]
+        else:
+            q = -0.5 * (B + np.copysign(np.sqrt(max(B * B - 4.0 * A * C, 0.0)), B))
+            cand = [q / A, C / q]
+        cand = [t for t in cand if 2.0 * A * t + B <= 0.0]      # where the derivative falls: the maximum
+        t = min(cand, key=lambda t: abs(t - 0.5))
+        k_out.append(x[j] + min(max(t, 0.0), 1.0) * h)
+    k_out = np.array(k_out, dtype=np.float64)
+    return k_out, (np.asarray(f(k_out), dtype=np.complex128) if len(k_out) else np.zeros(0, dtype=np.complex128))
+
+
 def write_vtk(dump_file, x, y, z, variables, names):
     """Legacy-VTK structured-grid dump of scalar fields on an irregular grid, byte for byte what the reference's
     `makeDumpVTK(x, y, z, variables, varList, dumpFile)` writes (Cylinder/Non-uniform density/Coronal/Movies/

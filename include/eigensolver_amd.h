@@ -874,12 +874,68 @@ int es_shoot_mode_signature(es_context* ctx, const es_problem* prob, const doubl
  *     min(max(*d_count, 0), n) and leaves entries beyond it alone.
  *     Asynchronous on the context's stream, no host synchronisation.  n == 0 succeeds and touches nothing (the arrays may
  *     then be NULL).  ES_ERR_INVALID_ARG: n < 0, a null problem, d_k or d_w null with n > 0; ES_ERR_UNSUPPORTED: an unknown
- *     family.  Not offered: complex frequencies (section 6) and the closed-form uniform cylinder (section 4).
+ *     family.  Not offered: the closed-form uniform cylinder (section 4).  Complex frequencies (section 6) have their own
+ *     call, es_complex_root_slopes of section 12.
  * ====================================================================================================== */
 int es_shoot_root_slopes(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w, int n,
                          const int32_t* d_count /* may be NULL */,
                          double* d_outer /* [3][n]: value, d/dw, d/dk */, double* d_inner /* [3][n] */,
                          uint8_t* d_status);
+
+/* ======================================================================================================
+ * (12) Slopes and Newton tracing of complex roots of the flow slab (the unstable, Kelvin-Helmholtz modes of section 6).
+ *     D_c(k, omega) of es_complex_eval_points is holomorphic in omega; with D_w = dD_c/d omega and D_k = dD_c/dk (k real)
+ *       d omega / dk = -D_k / D_w:  the real part is the group speed, the imaginary part the slope of the growth rate,
+ *                                   whose zero marks the most unstable wavenumber;
+ *       -D_c / D_w              :  the Newton correction, quadratic because D_c is holomorphic (section 6 takes 12 secant
+ *                                   steps from a cell centre).
+ *     Both calls take `variant` and the problem as section 6 does (ES_GEOM_SLAB_FLOW only) and report what it reports for a
+ *     bad variant (ES_ERR_INVALID_ARG) or another geometry (ES_ERR_UNSUPPORTED).  Both are asynchronous on the context's
+ *     stream, no host synchronisation; n == 0 succeeds and touches nothing (the arrays may then be NULL).  d_count (may be
+ *     NULL): as in section 10 -- the kernels use min(max(*d_count, 0), n) and leave entries beyond it alone.
+ *
+ *     es_complex_root_slopes: one (k, omega) pair per lane; the coefficient functions, the adjoint RK4 march, the closed-form
+ *     exterior and the boundary algebra of es_complex_eval_points carried in jets of three complex components (value,
+ *     d/d omega, d/dk) -- exact to rounding, no step to choose (beside a critical layer no difference step is safe,
+ *     DESIGN.md section 8g).
+ *       d_outer / d_inner [3][n][2]: (re, im) pairs; row 0 the value, row 1 d/d omega, row 2 d/dk of the total pressure
+ *         outside and inside.  outer - inner of row 0 is the D_c of es_complex_eval_points (the same operations in the same
+ *         order); D_w and D_k are the differences of rows 1 and 2.  The rows are n apart, whatever d_count holds.
+ *       d_status [n]: the status es_complex_eval_points gives the pair.  A pair whose status is not ES_PT_OK, or one of
+ *         whose six outputs is not finite, gets NaN in all six; the other pairs do not depend on it.
+ *     Any of the three output pointers may be NULL: that output is skipped.
+ *     ES_ERR_INVALID_ARG: n < 0, a null problem, d_k, d_w_re or d_w_im null with n > 0.
+ *
+ *     es_complex_newton: one guess per lane, Newton's iteration in omega at fixed k:
+ *         w = guess; iters = 0; ok = true
+ *         repeat max_iter times:
+ *             D, D_w, status at w
+ *             if status != ES_PT_OK or D, D_w not finite or D_w == 0:  ok = false; stop
+ *             s = -D / D_w;  if |s| > step_cap: s *= step_cap / |s|
+ *             w += s; iters += 1
+ *             if |s| <= 1e-14 max(1, |w|): stop
+ *         at the final w:  resid = 100 |D| / max(|outer|, |inner|),  dwdk = -D_k / D_w,  status
+ *         flag = ok && status == ES_PT_OK && resid < tol_percent && |w - guess| <= max_shift
+ *       d_w_re, d_w_im, d_resid, d_iters, d_flag [n]; d_dwdk [n][2] (re, im; may be NULL).  w is reported whatever the flag;
+ *       resid and dwdk are NaN where the final status is not ES_PT_OK.  max_iter == 0 is the final evaluation alone: the
+ *       guess with its resid and slope.  Pass DBL_MAX for no step_cap / max_shift.
+ *       At a branch point -- where a conjugate pair of roots meets on the real axis -- D_w = 0: dwdk is then not finite
+ *       and the iteration stops with ok = false if it lands there exactly; nothing else is done about it.
+ *     ES_ERR_INVALID_ARG: n < 0, max_iter < 0, step_cap, max_shift or tol_percent not positive, a null problem, any array
+ *     but d_count and d_dwdk null with n > 0.
+ * ====================================================================================================== */
+int es_complex_root_slopes(es_context* ctx, const es_problem* prob, int variant,
+                           const double* d_k, const double* d_w_re, const double* d_w_im, int n,
+                           const int32_t* d_count /* may be NULL */,
+                           double* d_outer /* [3][n][2]: value, d/dw, d/dk; (re, im) pairs */,
+                           double* d_inner /* [3][n][2] */, uint8_t* d_status);
+
+int es_complex_newton(es_context* ctx, const es_problem* prob, int variant,
+                      const double* d_k, const double* d_guess_re, const double* d_guess_im, int n,
+                      const int32_t* d_count /* may be NULL */,
+                      int max_iter, double step_cap, double max_shift, double tol_percent,
+                      double* d_w_re, double* d_w_im, double* d_resid,
+                      double* d_dwdk /* [n][2], may be NULL */, int32_t* d_iters, int32_t* d_flag);
 
 #ifdef __cplusplus
 }
