@@ -1,153 +1,21 @@
 // K6: complex-frequency determinant of the flow slab, winding-number cell detection and complex secant refinement,
 // eigenfunctions at given complex (k, omega).
 // See include/eigensolver_amd.h section (6) for the reference lines this replaces and oracle/slab_complex.py for the
-// CPU restatement (same algorithm: closed-form exterior, adjoint RK4 on the reference's ix grid with mid-point
-// coefficient sets, far-end condition by superposition).
-//
-// One (k, omega) point per lane.  The profile table (U, U', U'' at nodes and mid-points) is staged in LDS chunk by
-// chunk as in shoot_point; every lane forms its own complex coefficients.  This path is a handful of complex
-// divisions per node and is not on the benchmark path: written for clarity, IEEE divisions throughout.
+// CPU restatement.  The formulas (coefficients, exterior, adjoint march, boundary) are the W = 1 instances of
+// es_complex_shared.hpp, the text es_complex_slopes.hip differentiates; here are the kernels around them: one (k, omega)
+// point per lane, the forward march of the eigenfunction, the winding-number flags and the secant refinement.
 #include "es_complex_shared.hpp"
 
 namespace {
 using namespace es_complex_shared;
+using cv = cj<1>;                    // the plain complex value as the formulas take it
 
-// interior coefficients at one node: u' = v, v' = a21 u + a22 v  with  a21 = -coeff, a22 = -D
-struct CxCoef { cx a21, a22; };
-
-__device__ __forceinline__ void cx_terms(const CxConsts& C, cx w, double U, double dU, cx& Om, cx& Om2, cx& m0, cx& D) {
-  Om = w - mk(C.k * U);
-  Om2 = Om * Om;
-  const cx n1 = C.kc2 - Om2, n3 = C.kvA2 - Om2, nT = C.kcT2 - Om2;
-  m0 = (n1 * n3) / (C.S_i * nT);                                                     // SF-X:375
-  const double kdU2 = 2.0 * C.k * dU;
-  if (C.variant == ES_CX_SFX) {
-    D = kdU2 * ((Om2 / (Om2 - mk(C.kc2)) - mk(C.kcT2) / (Om2 - mk(C.kcT2))) / Om);   // SF-X:382
-  } else {
-    const cx t = Om2 - mk(C.kcT2);
-    D = kdU2 * ((t + mk(C.k4c) / (C.S_i * t)) / (Om * (Om2 - mk(C.kc2))));          // SF-G:421 as written
-  }
-}
-
-__device__ __forceinline__ CxCoef cx_coef(const CxConsts& C, cx w, double U, double dU, double ddU) {
-  cx Om, Om2, m0, D;
-  cx_terms(C, w, U, dU, Om, Om2, m0, D);
-  const cx coeff = mk(C.k * ddU) / Om + (C.k * dU) * (D / Om) - m0;                   // SF-X:389
-  return CxCoef{-coeff, -D};
-}
-
-// rhs of the transposed system: A^T z with A = [[0, 1], [a21, a22]]
-__device__ __forceinline__ void cx_rhs(const CxCoef& A, cx p, cx q, cx& kp, cx& kq) {
-  kp = A.a21 * q;
-  kq = p + A.a22 * q;
-}
-
-// exterior (closed form, decaying branch), SF-X:369-371, :419-426:  Vx_e ~ gp e^{mu (x + R)} + gm e^{-mu (x + R)}
-struct CxExt {
-  cx Oe, p_e, mu, gp, gm, E2;      // E2 = e^{-2 mu (R - 1)}
-  cx outer;                        // p_e V_e'(-1) / V_e(-1)
-  double R;
-  int status;
-};
-
-__device__ __forceinline__ CxExt cx_exterior(const ShootDev& P, const CxConsts& C, double k, cx w) {
-  CxExt X;
-  X.Oe = w - mk(k * P.U_e);
-  const cx Oe2 = X.Oe * X.Oe;
-  const cx m_e = ((C.k2 * P.vAe2 - Oe2) * (C.k2 * P.ce2 - Oe2)) / (P.Se * (C.k2 * P.cTe2 - Oe2));
-  X.p_e = (P.rho_e * P.Se) * ((C.k2 * P.cTe2 - Oe2) / (X.Oe * (C.k2 * P.ce2 - Oe2)));
-  X.status = ES_PT_OK;
-  if (m_e.re < 0.0) X.status = ES_PT_LEAKY;                                           // `if m_e.real < 0: pass`
-  X.mu = csqrt_(m_e);
-  X.R = P.R_factor / k;
-  X.E2 = cexp_((-2.0 * (X.R - 1.0)) * X.mu);
-  const cx gq = mk(P.ic1) / X.mu;
-  X.gp = P.ic0 + gq; X.gm = P.ic0 - gq;
-  const cx y = X.mu * ((X.gp - X.E2 * X.gm) / (X.gp + X.E2 * X.gm));
-  X.outer = X.p_e * y;
-  if (X.status == ES_PT_OK && !cfinite(X.outer)) X.status = ES_PT_NONFINITE;
-  return X;
-}
-
-// adjoint march of the functional Vx(+1) = (1, 0) . (u, v) from x = +1 back to x = -1: Vx(+1) = zp u(-1) + zq v(-1).
-// Ub, dUb: the profile at the boundary node.  Every lane of the workgroup must call this (barriers of the staging).
-__device__ __forceinline__ void cx_adjoint(const ShootDev& P, const CxConsts& C, cx w, double* __restrict__ sb, cx& zp,
-                                           cx& zq, double& Ub, double& dUb) {
-  constexpr int NB = 3;
-  const int nsteps = P.n_nodes - 1;
-  const double h = P.h, h2 = 0.5 * P.h, h6 = P.h / 6.0, h3 = P.h / 3.0;
-  zp = mk(1.0); zq = mk(0.0);
-  CxCoef B0{mk(0.0), mk(0.0)};
-  Ub = 0.0; dUb = 0.0;
-  const int nchunks = (nsteps + CH - 1) / CH;
-  for (int c = nchunks - 1; c >= 0; --c) {
-    const int c0 = c * CH;
-    const int nst = (nsteps - c0 < CH) ? (nsteps - c0) : CH;
-    __syncthreads();
-#pragma unroll
-    for (int f = 0; f < NB; ++f)
-      for (int i = threadIdx.x; i < 2 * nst + 1; i += blockDim.x) sb[i * NB + f] = P.base[(size_t)f * P.npts + 2 * c0 + i];
-    __syncthreads();
-    if (c == nchunks - 1) B0 = cx_coef(C, w, sb[2 * nst * NB + SF_U], sb[2 * nst * NB + SF_DU], sb[2 * nst * NB + SF_DDU]);
-    for (int j = nst - 1; j >= 0; --j) {
-      const double* bm = sb + (2 * j + 1) * NB;
-      const double* b1 = sb + (2 * j) * NB;
-      const CxCoef Bm = cx_coef(C, w, bm[SF_U], bm[SF_DU], bm[SF_DDU]);
-      const CxCoef B1 = cx_coef(C, w, b1[SF_U], b1[SF_DU], b1[SF_DDU]);
-      cx k1p, k1q, k2p, k2q, k3p, k3q, k4p, k4q;
-      cx_rhs(B0, zp, zq, k1p, k1q);
-      cx_rhs(Bm, zp + h2 * k1p, zq + h2 * k1q, k2p, k2q);
-      cx_rhs(Bm, zp + h2 * k2p, zq + h2 * k2q, k3p, k3q);
-      cx_rhs(B1, zp + h * k3p, zq + h * k3q, k4p, k4q);
-      zp = zp + h6 * (k1p + k4p) + h3 * (k2p + k3p);
-      zq = zq + h6 * (k1q + k4q) + h3 * (k2q + k3q);
-      B0 = B1;
-      if (c == 0 && j == 0) { Ub = b1[SF_U]; dUb = b1[SF_DU]; }
-    }
-  }
-}
-
-// total pressure of the interior state (u, v) = (Vx, Vx') at a node with Omega = Om: P_Ti (v - add u), SF-X:395, :401, :455
-__device__ __forceinline__ cx cx_total_pressure(const ShootDev& P, const CxConsts& C, cx Om, cx Om2, double dU, cx u, cx v) {
-  const cx PTi = (P.rho_i * P.S_i) * ((C.kcT2 - Om2) / (Om * (C.kc2 - Om2)));         // SF-X:395
-  const cx add = (C.variant == ES_CX_SFX) ? -(mk(C.k * dU) / Om) : mk(0.0);           // SF-X:401
-  return PTi * (v - add * u);
-}
-
-// boundary: continuity of the displacement, symmetry condition by superposition, total pressures (SF-X:422, :455)
-struct CxBoundary {
-  cx Vb, sv;          // interior state at x = -1 per unit V_e(-1): Vx, Vx'
-  cx D;               // outer - inner, NaN unless st == ES_PT_OK
-  double rel;
-  uint8_t st;
-};
-
-__device__ __forceinline__ CxBoundary cx_boundary(const ShootDev& P, const CxConsts& C, const CxExt& X, cx w, cx zp, cx zq,
-                                                  double Ub, double dUb) {
-  CxBoundary B;
-  cx Omb, Omb2, m0b, Db;
-  cx_terms(C, w, Ub, dUb, Omb, Omb2, m0b, Db);
-  B.Vb = Omb / X.Oe;
-  B.sv = ((P.slab_sign - zp) * B.Vb) / zq;
-  const cx inner = cx_total_pressure(P, C, Omb, Omb2, dUb, B.Vb, B.sv);
-  const cx d = X.outer - inner;
-  B.st = (uint8_t)X.status;
-  B.D = d;
-  B.rel = cabs_(d) * 100.0 / fmax(cabs_(X.outer), cabs_(inner));
-  if (X.status != ES_PT_OK) { B.D = cx{NAN, NAN}; B.rel = NAN; return B; }
-  if (!cfinite(d)) { B.st = ES_PT_NONFINITE; B.D = cx{NAN, NAN}; B.rel = NAN; }
-  return B;
-}
-
+// D_c = outer - inner at one point, NaN unless st == ES_PT_OK.  Every lane of the workgroup must call this.
 __device__ __forceinline__ void cx_shoot_point(const ShootDev& P, int variant, double k, cx w, cx& D, double& rel,
                                                uint8_t& st, double* __restrict__ sb) {
-  const CxConsts C = cx_consts(P, variant, k);
-  const CxExt X = cx_exterior(P, C, k, w);
-  cx zp, zq;
-  double Ub, dUb;
-  cx_adjoint(P, C, w, sb, zp, zq, Ub, dUb);
-  const CxBoundary B = cx_boundary(P, C, X, w, zp, zq, Ub, dUb);
-  D = B.D; rel = B.rel; st = B.st;
+  const CxMatch<1> B = cx_eval<1>(P, variant, k, w, sb);
+  D = (B.st == ES_PT_OK) ? B.outer.c[0] - B.inner.c[0] : cx{NAN, NAN};
+  rel = B.rel; st = B.st;
 }
 
 __device__ __forceinline__ cx cx_pick_w(int w_mode, double k, double wre, double wim) {
@@ -160,7 +28,7 @@ __global__ __launch_bounds__(256) void cx_eval_kernel(ShootDev P, int variant, c
                                                       long n, int n_re, int n_im, int w_mode,
                                                       double* __restrict__ Dre, double* __restrict__ Dim,
                                                       double* __restrict__ relout, uint8_t* __restrict__ stout) {
-  __shared__ double sb[3 * (2 * CH + 1)];
+  __shared__ double sb[CX_LDS_DOUBLES];
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;
   double k = 1.0;
@@ -189,7 +57,7 @@ __global__ __launch_bounds__(256) void cx_eval_kernel(ShootDev P, int variant, c
 
 // ---- eigenfunctions at given (k, omega) -----------------------------------------------------------------------------
 // rhs of the forward system: A y with A = [[0, 1], [a21, a22]]
-__device__ __forceinline__ void cx_rhs_fwd(const CxCoef& A, cx u, cx v, cx& ku, cx& kv) {
+__device__ __forceinline__ void cx_rhs_fwd(const CxNode<1>& A, const cv& u, const cv& v, cv& ku, cv& kv) {
   ku = v;
   kv = A.a21 * u + A.a22 * v;
 }
@@ -202,55 +70,51 @@ __global__ __launch_bounds__(64) void cx_eigen_interior_kernel(ShootDev P, int v
                                                                const double* __restrict__ wim, int n,
                                                                double* __restrict__ val, double* __restrict__ flux,
                                                                uint8_t* __restrict__ stout) {
-  constexpr int NB = 3;
-  __shared__ double sb[3 * (2 * CH + 1)];
+  constexpr int NB = CX_NB;
+  __shared__ double sb[CX_LDS_DOUBLES];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;
   const double k = in ? kv[i] : 1.0;
   const cx w = in ? cx{wre[i], wim[i]} : cx{1.0, 0.1};
   const CxConsts C = cx_consts(P, variant, k);
-  const CxExt X = cx_exterior(P, C, k, w);
-  // (1) the row of the transfer matrix picked by the far-end condition -> boundary state, D_c and status
-  cx zp, zq;
+  const CxOutside<1> X = cx_exterior<1>(P, C, k, w);
+  // (1) the row of the transfer matrix picked by the far-end condition -> boundary state and status
+  cv zp, zq;
   double Ub, dUb;
-  cx_adjoint(P, C, w, sb, zp, zq, Ub, dUb);
-  const CxBoundary B = cx_boundary(P, C, X, w, zp, zq, Ub, dUb);
+  cx_adjoint<1>(P, C, w, sb, zp, zq, Ub, dUb);
+  const CxMatch<1> B = cx_boundary<1>(P, C, X, w, zp, zq, Ub, dUb);
   const bool ok = B.st == ES_PT_OK;
   if (in) stout[i] = B.st;
   // (2) forward march from the boundary, writing every node
-  cx u = B.Vb, v = B.sv;
+  cv u = B.Vb, v = B.sv;
   auto store = [&](int node, double U, double dU) {
     if (!in) return;
-    const cx Om = w - mk(k * U);
-    const cx pt = cx_total_pressure(P, C, Om, Om * Om, dU, u, v);
+    const cv Om = doppler<1>(w, k, U);
+    const cx pt = cx_total_pressure<1>(P, C, Om, Om * Om, dU, u, v).c[0];
     const size_t o = 2 * ((size_t)i * P.n_nodes + node);
-    val[o] = ok ? u.re : NAN;
-    val[o + 1] = ok ? u.im : NAN;
+    val[o] = ok ? u.c[0].re : NAN;
+    val[o + 1] = ok ? u.c[0].im : NAN;
     flux[o] = ok ? pt.re : NAN;
     flux[o + 1] = ok ? pt.im : NAN;
   };
   const int nsteps = P.n_nodes - 1;
   const double h = P.h, h2 = 0.5 * P.h, h6 = P.h / 6.0, h3 = P.h / 3.0;
-  CxCoef A0{mk(0.0), mk(0.0)};
+  CxNode<1> A0{jconst<1>(0.0), jconst<1>(0.0)};
   const int nchunks = (nsteps + CH - 1) / CH;
   for (int c = 0; c < nchunks; ++c) {
     const int c0 = c * CH;
     const int nst = (nsteps - c0 < CH) ? (nsteps - c0) : CH;
-    __syncthreads();
-#pragma unroll
-    for (int f = 0; f < NB; ++f)
-      for (int t = threadIdx.x; t < 2 * nst + 1; t += blockDim.x) sb[t * NB + f] = P.base[(size_t)f * P.npts + 2 * c0 + t];
-    __syncthreads();
+    cx_stage_chunk(P, c0, nst, sb);
     if (c == 0) {
-      A0 = cx_coef(C, w, sb[SF_U], sb[SF_DU], sb[SF_DDU]);
+      A0 = cx_coef<1>(C, w, sb[SF_U], sb[SF_DU], sb[SF_DDU]);
       store(0, sb[SF_U], sb[SF_DU]);
     }
     for (int j = 0; j < nst; ++j) {
       const double* bm = sb + (2 * j + 1) * NB;
       const double* b1 = sb + (2 * j + 2) * NB;
-      const CxCoef Am = cx_coef(C, w, bm[SF_U], bm[SF_DU], bm[SF_DDU]);
-      const CxCoef A1 = cx_coef(C, w, b1[SF_U], b1[SF_DU], b1[SF_DDU]);
-      cx k1u, k1v, k2u, k2v, k3u, k3v, k4u, k4v;
+      const CxNode<1> Am = cx_coef<1>(C, w, bm[SF_U], bm[SF_DU], bm[SF_DDU]);
+      const CxNode<1> A1 = cx_coef<1>(C, w, b1[SF_U], b1[SF_DU], b1[SF_DDU]);
+      cv k1u, k1v, k2u, k2v, k3u, k3v, k4u, k4v;
       cx_rhs_fwd(A0, u, v, k1u, k1v);
       cx_rhs_fwd(Am, u + h2 * k1u, v + h2 * k1v, k2u, k2v);
       cx_rhs_fwd(Am, u + h2 * k2u, v + h2 * k2v, k3u, k3v);
@@ -275,18 +139,19 @@ __global__ __launch_bounds__(256) void cx_eigen_exterior_kernel(ShootDev P, int 
   const int i = (int)(t / n_ext), j = (int)(t - (long)i * n_ext);
   const double k = kv[i];
   const cx w = cx{wre[i], wim[i]};
-  const CxExt X = cx_exterior(P, cx_consts(P, variant, k), k, w);
+  const CxOutside<1> X = cx_exterior<1>(P, cx_consts(P, variant, k), k, w);
+  const cx mu = X.mu.c[0], gp = X.gp.c[0], gm = X.gm.c[0];
   // np.linspace(-R, -1, n_ext)[j]
   const double step = (-1.0 + X.R) / (double)(n_ext - 1);
   const double x = (j == n_ext - 1) ? -1.0 : -X.R + (double)j * step;
   const double ax = fabs(x);
   cx v = cx{NAN, NAN}, f = cx{NAN, NAN};
   if (st[i] == ES_PT_OK) {
-    const cx E2x = cexp_((-2.0 * (X.R - ax)) * X.mu);
-    const cx dec = cexp_((-(ax - 1.0)) * X.mu);
-    const cx den = X.gp + X.E2 * X.gm;
-    v = dec * ((X.gp + E2x * X.gm) / den);
-    f = X.p_e * (X.mu * (dec * ((X.gp - E2x * X.gm) / den)));                         // left_P = p_e_const * Vx'
+    const cx E2x = cexp_((-2.0 * (X.R - ax)) * mu);
+    const cx dec = cexp_((-(ax - 1.0)) * mu);
+    const cx den = gp + X.E2.c[0] * gm;
+    v = dec * ((gp + E2x * gm) / den);
+    f = X.p_e.c[0] * (mu * (dec * ((gp - E2x * gm) / den)));                           // left_P = p_e_const * Vx'
   }
   xs[t] = x;
   val[2 * t] = v.re;
@@ -355,7 +220,7 @@ __global__ __launch_bounds__(64) void cx_refine_kernel(ShootDev P, int variant, 
                                                        const double* __restrict__ half_re,
                                                        const double* __restrict__ half_im, int n, int n_iter,
                                                        double tol_percent) {
-  __shared__ double sb[3 * (2 * CH + 1)];
+  __shared__ double sb[CX_LDS_DOUBLES];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;
   const double k = in ? tab.d_k[i] : 1.0;

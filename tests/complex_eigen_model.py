@@ -41,20 +41,22 @@ def _coef(o, x, k, w):
     return -cf, -D                                           # a21, a22 (a11 = 0, a12 = 1)
 
 
-def adjoint_rk4(o, k, w):
-    """(zp, zq): the row (T11, T12) of the transfer matrix from -1 to +1, by the transposed march of eval_rk4."""
+def adjoint_rk4(o, k, w, coef=_coef, start=None):
+    """(zp, zq): the row (T11, T12) of the transfer matrix from -1 to +1, by the transposed march of eval_rk4.
+    coef(o, x, k, w) -> (a21, a22) and start = (p, q) at x = +1 (default: 1, 0) let another number type make the same
+    march (tests/complex_slope_model.py: jets)."""
     N = o.n_nodes
     x = np.linspace(-1.0, 1.0, 2 * N - 1)
     h = 2.0 / (N - 1)
-    p, q = np.ones_like(w), np.zeros_like(w)
+    p, q = (np.ones_like(w), np.zeros_like(w)) if start is None else start
 
     def rhs(a, pp, qq):
         return a[0] * qq, pp + a[1] * qq
 
     with np.errstate(all="ignore"):
-        B0 = _coef(o, x[2 * (N - 1)], k, w)
+        B0 = coef(o, x[2 * (N - 1)], k, w)
         for j in range(N - 2, -1, -1):
-            Bm, B1 = _coef(o, x[2 * j + 1], k, w), _coef(o, x[2 * j], k, w)
+            Bm, B1 = coef(o, x[2 * j + 1], k, w), coef(o, x[2 * j], k, w)
             k1p, k1q = rhs(B0, p, q)
             k2p, k2q = rhs(Bm, p + 0.5 * h * k1p, q + 0.5 * h * k1q)
             k3p, k3q = rhs(Bm, p + 0.5 * h * k2p, q + 0.5 * h * k2q)

@@ -138,29 +138,12 @@ def jets(o, k, w):
         outer = p_e * (mu * (gp - E2 * gm) / (gp + E2 * gm))
         st = np.where(m_e.v.real < 0.0, ST_LEAKY, ST_OK)
         st = np.where((st == ST_OK) & ~np.isfinite(outer.v), ST_NONFINITE, st)
-        # interior (ComplexFlowSlab.eval_rk4)
-        N = o.n_nodes
-        x = np.linspace(-1.0, 1.0, 2 * N - 1)
-        h = 2.0 / (N - 1)
-
-        def A(i):
-            D, cf, _, _ = _interior(o, x[i], kj, wj)
+        # interior (ComplexFlowSlab.eval_rk4): the adjoint march of the eigenfunction model, over jets
+        def coef(o, x, k, w):
+            D, cf, _, _ = _interior(o, x, k, w)
             return -cf, -D
 
-        def rhs(a, pp, qq):
-            return a[0] * qq, pp + a[1] * qq
-
-        p, q = J(one, zero, zero), J(zero, zero, zero)
-        B0 = A(2 * (N - 1))
-        for j in range(N - 2, -1, -1):
-            Bm, B1 = A(2 * j + 1), A(2 * j)
-            k1p, k1q = rhs(B0, p, q)
-            k2p, k2q = rhs(Bm, p + 0.5 * h * k1p, q + 0.5 * h * k1q)
-            k3p, k3q = rhs(Bm, p + 0.5 * h * k2p, q + 0.5 * h * k2q)
-            k4p, k4q = rhs(B1, p + h * k3p, q + h * k3q)
-            p = p + h / 6.0 * (k1p + k4p) + h / 3.0 * (k2p + k3p)
-            q = q + h / 6.0 * (k1q + k4q) + h / 3.0 * (k2q + k3q)
-            B0 = B1
+        p, q = E.adjoint_rk4(o, kj, wj, coef=coef, start=(J(one, zero, zero), J(zero, zero, zero)))
         # ComplexFlowSlab._finish
         sigma = -1.0 if o.mode == "sausage" else 1.0
         Vb = (wj - kj * float(o.U(-1.0))) / (wj - kj * o.U_e)

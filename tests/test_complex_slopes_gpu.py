@@ -3,7 +3,8 @@
 
 Yardsticks (tests/complex_slope_model.py, pinned on the CPU by tests/test_complex_slope_model.py):
   value    outer - inner of row 0 against the D_c of es_complex_eval_points at the same pairs: 1e-12 of max(|outer|, |inner|),
-           the bound tests/test_root_slopes_gpu.py uses for the same comparison.
+           the bound tests/test_root_slopes_gpu.py uses for the same comparison -- and bit for bit, since both paths run the
+           one text of es_complex_shared.hpp (so is the resid of a Newton call that takes no step against rel).
   jets     the NumPy forward-mode restatement of the oracle: every row of outer and inner within 1e-10 of
            max(|outer_x|, |inner_x|), the project's bound for the GPU against a NumPy restatement.
   slope    d omega / dk against the slope of the oracle's root curve, with the bounds the CPU test fixed.
@@ -88,6 +89,8 @@ def test_value_is_the_determinant_of_eval_points(pool, width, mode, variant):
         print(f"{mode} {variant} width {width} N {N}: worst |(outer - inner) - D_c| / max(|outer|, |inner|) = {err.max():.2e} "
               f"over {len(D)} pairs (bound 1.0e-12)")
         assert err.max() <= 1e-12, (N, err)
+        # one text at jet widths 1 and 3, no contraction: row 0 is the value path's arithmetic, operation for operation
+        assert np.array_equal(g["outer"][0] - g["inner"][0], D), N
 
 
 @pytest.mark.parametrize("width,mode,variant", CASES)
@@ -364,6 +367,28 @@ def test_newton_guards(pool):
     assert g["flag"].tolist() == [0, 0] and abs(g["w"][0] - root) <= 1e-12 and g["resid"][0] < 1e-6
     g = _host(s.newton("kink", C.K0, [guess], max_shift=2e-2, tol_percent=1e-6))
     assert g["flag"].tolist() == [1] and abs(g["w"][0] - root) <= 1e-12
+
+
+@pytest.mark.parametrize("N", (3, 130))
+def test_newton_without_steps_is_eval_points(pool, N):
+    """max_iter = 0 on 65 guesses (one full workgroup and a ragged one), a different k in every lane, the leaky pair among
+    them: w is the guess and resid the rel of es_complex_eval_points at the guesses, bit for bit (one text at jet widths 1
+    and 3); flag = 1 where the point is ES_PT_OK with rel < tol_percent."""
+    s = pool.solver(0.9, "sfx", N)
+    guess = C.NON_ROOT + 0.004 * np.arange(65) * (1 - 0.5j)
+    k = C.K0 + 1e-3 * np.arange(65)
+    guess[40], k[40] = C.LEAKY, C.K0
+    _, st, rel = s.eval_points("kink", k, guess)
+    st, rel = st.cpu().numpy(), rel.cpu().numpy()
+    assert st[40] == 1 and np.all(np.delete(st, 40) == 0) and np.isfinite(np.delete(rel, 40)).all()
+    tol = float(np.median(np.delete(rel, 40)))                                          # none of the guesses is a root
+    g = _host(s.newton("kink", k, guess, max_iter=0, tol_percent=tol))
+    assert np.array_equal(g["w"].real, guess.real) and np.array_equal(g["w"].imag, guess.imag)
+    assert g["iters"].tolist() == [0] * 65
+    assert np.array_equal(g["resid"], rel, equal_nan=True)
+    assert np.isnan(g["resid"][40]) and np.isnan(rel[40]) and g["flag"][40] == 0
+    assert g["flag"].tolist() == [1 if (a == 0 and r < tol) else 0 for a, r in zip(st, rel)]
+    assert 0 < g["flag"].sum() < 64
 
 
 # ---- densify and most_unstable ----------------------------------------------------------------------------------------------

@@ -8,6 +8,9 @@ repeat in one process so that drift hits all alike, every buffer allocated befor
       stencil       ONE es_complex_eval_points on 5 n pairs: the centre, omega +- h and k +- h -- the central differences one
                     would otherwise take (h = 2^-10; beside a critical layer no step is safe)
       eval_points   ONE es_complex_eval_points on the n pairs -- the scale of the call, not a target
+      eigenfunction es_complex_eigenfunction on the first 2^12 of the pairs with n_ext = 2: the adjoint march, the forward
+                    march that writes every node and the exterior kernel -- with it every kernel that runs the formulas of
+                    es_complex_shared.hpp has a timed leg
   densify    the unstable branch of the uniform-flow slab (kink, "sfx", N = 500) at 256 wavenumbers in [0.3, 0.6]:
       scan          the path without slopes: es_complex_eval_grid + es_complex_find_roots at the 256 rows on the 16 x 12
                     window of tests/complex_eigen_model.py (12 secant steps per flagged cell; the call reads its count back)
@@ -15,8 +18,8 @@ repeat in one process so that drift hits all alike, every buffer allocated befor
                     slopes at 9 roots, the Hermite prediction in torch, one es_complex_newton over the 256 points
   Before timing, the roots of the two densify legs are compared row by row.
 
---lib: another build of the library.  One that lacks section 12 (the parent commit's) times the `eval_points`, `stencil` and
-`scan` legs only -- its line is the scan path's timing before this call existed.
+--lib: another build of the library.  One that lacks section 12 times the `eval_points`, `stencil`, `eigenfunction` and
+`scan` legs only -- its line is the scan path's timing before that section existed.
 
     python tools/time_complex_slopes.py [--repeats 20] [--warmup 3] [--lib PATH] [--out profiles/complex_slopes_timing.jsonl]
 """
@@ -117,6 +120,11 @@ def main():
         st5 = torch.empty(5 * n, dtype=torch.uint8, device=dev)
         D1 = [torch.empty(n, dtype=torch.float64, device=dev) for _ in range(2)]
         st1 = torch.empty(n, dtype=torch.uint8, device=dev)
+        ne, n_ext = min(n, 1 << 12), 2
+        vi, fi = (torch.empty((ne, a.nodes), dtype=torch.complex128, device=dev) for _ in range(2))
+        xe = torch.empty((ne, n_ext), dtype=torch.float64, device=dev)
+        ve, fe = (torch.empty((ne, n_ext), dtype=torch.complex128, device=dev) for _ in range(2))
+        ste = torch.empty(ne, dtype=torch.uint8, device=dev)
 
     def slopes():
         _lib.check(ctx.handle, lib.es_complex_root_slopes(ctx.handle, p.handle, s.variant, P(k), P(wre), P(wim), n, None,
@@ -130,7 +138,11 @@ def main():
         _lib.check(ctx.handle, lib.es_complex_eval_points(ctx.handle, p.handle, s.variant, P(k), P(wre), P(wim), n, P(D1[0]),
                                                           P(D1[1]), None, P(st1)))
 
-    legs = {"stencil": stencil, "eval_points": eval_points}
+    def eigenfunction():
+        _lib.check(ctx.handle, lib.es_complex_eigenfunction(ctx.handle, p.handle, s.variant, P(k), P(wre), P(wim), ne, P(vi),
+                                                            P(fi), n_ext, P(xe), P(ve), P(fe), P(ste)))
+
+    legs = {"stencil": stencil, "eval_points": eval_points, "eigenfunction": eigenfunction}
     if full:
         legs = {"slopes": slopes, **legs}
     with torch.cuda.stream(stream):
@@ -146,7 +158,7 @@ def main():
             slope, slope5 = -d[2] / d[1], -(S5[3] - S5[4]) / (S5[1] - S5[2])
             diff = ((slope - slope5).abs() / slope.abs().clamp(min=1.0))[ok]
             line["slope_vs_stencil_median"], line["slope_vs_stencil_max"] = float(diff.median().item()), float(diff.max().item())
-    line["pairs"], line["stencil_step"] = n, STEP
+    line["pairs"], line["stencil_step"], line["eigenfunction_pairs"] = n, STEP, ne
     line["slopes_legs"] = timed(torch, stream, a, legs)
 
     # ---- densify against the scan ----------------------------------------------------------------------------------------
