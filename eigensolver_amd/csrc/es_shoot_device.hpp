@@ -73,17 +73,27 @@ enum { CT_MB = 0 /* m B_phi/r */, CT_BZ, CT_BA, CT_MV /* m v_phi/r */, CT_VZ, CT
 enum { SD_RHO = 0, SD_C2, SD_VA2 };
 enum { SF_U = 0, SF_DU, SF_DDU };
 
-struct Coef { double a11, a12, a21, a22; };
+// The formulas below are ONE text over a scalar type Num.  Num = double is every value kernel (and what oracle/c/shoot_port.c
+// mirrors); Num = Jet3 of es_slopes.hip carries (value, d/d omega, d/d k) through the same operations and brings its own
+// operators and overloads of fma, sqrt, exp, fabs, ldexp, fast_rcp, ke_pair, ie_pair_from_k and val.  val(x) is the value
+// component: what the text branches on and tracks signs of.  (Num, not T: T is a term of the twisted family's coefficients.)
+__device__ __forceinline__ double val(double x) { return x; }
+
+template <class Num> struct CoefT { Num a11, a12, a21, a22; };
+using Coef = CoefT<double>;
 
 // per-(k, m) scalars that do not depend on the node
-struct KScal {
-  double k, k2, m, m2;
-  double kc2, kvA2, kcT2, k4c;   // flow slab only
+template <class Num> struct KScalT {
+  Num k, k2;
+  double m, m2;
+  Num kc2, kvA2, kcT2, k4c;      // flow slab only
   double h2;                     // half RK4 step (scaled coefficient form of the untwisted cylinder, make_entry<.., true>)
 };
+using KScal = KScalT<double>;
 
-__device__ __forceinline__ KScal make_kscal(const ShootDev& P, double k) {
-  KScal s;
+template <class Num>
+__device__ __forceinline__ KScalT<Num> make_kscal(const ShootDev& P, Num k) {
+  KScalT<Num> s;
   s.k = k; s.k2 = k * k; s.m = (double)P.m; s.m2 = s.m * s.m;
   s.kc2 = s.k2 * P.c2_i; s.kvA2 = s.k2 * P.vA2_i; s.kcT2 = s.k2 * P.cT2_i;
   s.k4c = s.k2 * s.k2 * P.cT2_i * P.c2_i;
@@ -95,45 +105,47 @@ __device__ __forceinline__ KScal make_kscal(const ShootDev& P, double k) {
 // SCALED (FAM_CYL0 adjoint marches): the entries that become a12 and a21 carry the factor h/2, so that coef_pre /
 // coef_finish deliver (h/2) a12 and (h/2) a21 directly and the RK4 step needs no separate products with the step size
 // (rk4_step_adjoint_scaled0).
-template <int FAM, bool SCALED = false>
-__device__ __forceinline__ void make_entry(const double* b, const KScal& s, double* e) {
+// e receives the entries that depend on k, c those that are copies or products of base fields alone (for Num = Jet3 they stay
+// plain doubles; the value kernels pass one array for both: the three-argument form below).
+template <int FAM, bool SCALED = false, class Num>
+__device__ __forceinline__ void make_entry(const double* b, const KScalT<Num>& s, Num* e, double* c) {
   if (FAM == FAM_CYL0) {
-    const double wA = s.k * b[C0_BA];
-    const double wA2 = wA * wA;
+    const Num wA = s.k * b[C0_BA];
+    const Num wA2 = wA * wA;
     e[0] = s.k * b[C0_VZ];                     // Doppler shift k v_z
     e[1] = wA2;                                // omega_A^2
     e[2] = wA2 * b[C0_Q];                      // omega_c^2 = omega_A^2 c^2/(c^2+vA^2)
-    e[3] = b[C0_A1];                           // rho / r
+    c[3] = b[C0_A1];                           // rho / r
     // a21 = -r C2/(rho S t1 t2) with -r C2/(rho S) = g t2 - B (t2 + omega_c^2)^2, B = r/(rho S),
     // g = (m^2/r^2 + k^2) r/rho, t1 = t2 + omega_c^2 - omega_A^2.  Dividing the quadratic by t1 t2:
     //     a21 = -B + (lambda t2 + c0) / (t1 t2),   lambda = g - B (omega_A^2 + omega_c^2),   c0 = -B omega_c^4
     // so the numerator left over the denominator is LINEAR in t2 (one fma) and -B joins in the fma with 1/den.
     const double Bq = b[C0_B1];
-    const double g = s.m2 * b[C0_E1] + s.k2 * b[C0_E2];
-    e[4] = -Bq;
+    const Num g = s.m2 * b[C0_E1] + s.k2 * b[C0_E2];
+    c[4] = -Bq;
     e[5] = g - Bq * (e[1] + e[2]);
     e[6] = -(Bq * (e[2] * e[2]));
-    if (SCALED) { e[3] *= s.h2; e[4] *= s.h2; e[5] *= s.h2; e[6] *= s.h2; }
+    if (SCALED) { c[3] *= s.h2; c[4] *= s.h2; e[5] *= s.h2; e[6] *= s.h2; }
   } else if (FAM == FAM_CYLT) {
-    const double kb = fma(s.k, b[CT_BZ], b[CT_MB]);            // m B_phi/r + k B_z
-    const double wA = fma(s.k, b[CT_BA], b[CT_MB]);            // as written in the reference (CF:581)
-    const double wA2 = wA * wA;
+    const Num kb = fma(s.k, b[CT_BZ], b[CT_MB]);                 // m B_phi/r + k B_z
+    const Num wA = fma(s.k, b[CT_BA], b[CT_MB]);                 // as written in the reference (CF:581)
+    const Num wA2 = wA * wA;
     e[0] = fma(s.k, b[CT_VZ], b[CT_MV]);                       // shift: m v_phi/r + k v_z
     e[1] = wA2;
     e[2] = wA2 * b[CT_Q];
-    e[3] = b[CT_E3];                                           // rho S
-    e[4] = b[CT_RHO];
-    e[5] = b[CT_E5];                                           // q1 = rho v_phi^2 / r
-    e[6] = b[CT_E6];                                           // q2 = 2 B_phi^2 / r
+    c[3] = b[CT_E3];                                           // rho S
+    c[4] = b[CT_RHO];
+    c[5] = b[CT_E5];                                           // q1 = rho v_phi^2 / r
+    c[6] = b[CT_E6];                                           // q2 = 2 B_phi^2 / r
     e[7] = b[CT_C7] * kb * b[CT_INVR];                         // q3 = 2 B_phi v_phi kb / r
     e[8] = kb * b[CT_BPHI];                                    // tt1
-    e[9] = b[CT_E9];                                           // tt2 = rho v_phi
-    e[10] = b[CT_E10];                                         // c1c = 2 m S / r^2
+    c[9] = b[CT_E9];                                           // tt2 = rho v_phi
+    c[10] = b[CT_E10];                                         // c1c = 2 m S / r^2
     e[11] = b[CT_S] * (b[CT_M2R2] + s.k2);                     // c2c = S (m^2/r^2 + k^2)
-    e[12] = b[CT_RDC3];                                        // r d/dr[(B_phi/r)^2 - rho (v_phi/r)^2]
-    e[13] = b[CT_E13];                                         // c3b = 4 S / r^2
-    e[14] = b[CT_R];
-    e[15] = b[CT_INVR];
+    c[12] = b[CT_RDC3];                                        // r d/dr[(B_phi/r)^2 - rho (v_phi/r)^2]
+    c[13] = b[CT_E13];                                         // c3b = 4 S / r^2
+    c[14] = b[CT_R];
+    c[15] = b[CT_INVR];
   } else if (FAM == FAM_SLABD) {
     const double rho = b[SD_RHO], c2 = b[SD_C2], vA2 = b[SD_VA2];
     const double S = c2 + vA2;
@@ -141,14 +153,19 @@ __device__ __forceinline__ void make_entry(const double* b, const KScal& s, doub
     e[0] = s.k2 * c2;
     e[1] = s.k2 * cT2;
     e[2] = s.k2 * vA2;
-    e[3] = rho * S;
-    e[4] = rho;
+    c[3] = rho * S;
+    c[4] = rho;
   } else {
     e[0] = s.k * b[SF_U];
     e[1] = s.k * b[SF_DU];
     e[2] = s.k * b[SF_DDU];
     e[3] = 2.0 * e[1];
   }
+}
+
+template <int FAM, bool SCALED = false>
+__device__ __forceinline__ void make_entry(const double* b, const KScal& s, double* e) {
+  make_entry<FAM, SCALED>(b, s, e, e);
 }
 
 // sign tracking for the continuum / singular-point flag: the IEEE sign bits (high dwords) of every watched term are
@@ -192,101 +209,122 @@ __device__ __forceinline__ bool band_crossed(const ShootDev& P, double k, double
 // "/den" are numerators; coef_finish() multiplies them with 1/den.  The caller computes the reciprocals of the
 // mid-point and end-point denominators of a step with a single reciprocal (fast_rcp): inv = 1/(den_m * den_1),
 // 1/den_m = den_1 * inv, 1/den_1 = den_m * inv  (one reciprocal per RK4 step instead of two).
-struct CoefPre { double n11, n12, n21, n22, den; };
+template <class Num> struct CoefPreT { Num n11, n12, n21, n22, den; };
+using CoefPre = CoefPreT<double>;
 
 // C1P: c1_power of the twisted family as a compile-time constant (1 or 2), 0 = read it from the problem at run time.  The
 // one-point kernels branch once per evaluation (shoot_point) and march with the constant: the run-time select between Om and
 // Om^2 is two v_cndmask_b32 per node, four of the 113 instructions of a point-step there; same value either way.
-template <int FAM, bool TRACK = true, int C1P = 0>
-__device__ __forceinline__ void coef_pre(const double* e, const ShootDev& P, const KScal& s, double w, CoefPre& C,
-                                         SignTrack& st) {
+// The value kernels keep all node entries in one array and pass it for both e and c: read through e alone, as before the
+// text was generic.  (A second pointer read at one or two fixed offsets is turned into by-value arguments by the optimiser,
+// which then orders the operands of their products differently: same values, other encodings of the grid kernels.)
+template <class Num> __device__ __forceinline__ const double* entry_consts(const Num*, const double* c) { return c; }
+__device__ __forceinline__ const double* entry_consts(const double* e, const double*) { return e; }
+
+// e, c_: the k-dependent and the k-independent node entries, as make_entry fills them
+template <int FAM, bool TRACK = true, int C1P = 0, class Num>
+__device__ __forceinline__ void coef_pre(const Num* e, const double* c_, const ShootDev& P, const KScalT<Num>& s, Num w,
+                                         CoefPreT<Num>& C, SignTrack& st) {
+  const double* c = entry_consts(e, c_);
   if (FAM == FAM_CYL0) {
-    const double Om = w - e[0];
-    const double t1 = fma(Om, Om, -e[1]);                // Om^2 - omega_A^2
-    const double t2 = fma(Om, Om, -e[2]);                // Om^2 - omega_c^2
-    if (TRACK) { st.add(0, t1); st.add(1, t2); }
-    C.n11 = 0.0;
-    C.n12 = e[3] * t1;                                   // rho (Om^2 - wA^2) / r
+    const Num Om = w - e[0];
+    const Num t1 = fma(Om, Om, -e[1]);                   // Om^2 - omega_A^2
+    const Num t2 = fma(Om, Om, -e[2]);                   // Om^2 - omega_c^2
+    if (TRACK) { st.add(0, val(t1)); st.add(1, val(t2)); }
+    C.n11 = Num(0.0);
+    C.n12 = c[3] * t1;                                   // rho (Om^2 - wA^2) / r
     C.n21 = fma(e[5], t2, e[6]);                         // lambda t2 + c0              /den
-    C.n22 = e[4];                                        // -B, added after the division (coef_finish)
+    C.n22 = Num(c[4]);                                   // -B, added after the division (coef_finish)
     C.den = t1 * t2;
   } else if (FAM == FAM_CYLT) {
     // 23 fp64 instructions per node (33 until round 3, when every product-sum below was a multiply and an add): the sums
     // are explicit fused multiply-adds, grouped as in the fp32 screening kernel (coef_pre_f32); t2 T is formed once
-    const double Om = w - e[0];
-    const double Om2 = Om * Om;
-    const double t1 = Om2 - e[1];
-    const double t2 = Om2 - e[2];
-    if (TRACK) { st.add(0, t1); st.add(1, t2); }
-    const double D = e[3] * t1 * t2;
-    const double Q = fma(Om, e[7], fma(Om2, e[6], -(t1 * e[5])));
-    const double T = fma(e[9], Om, e[8]);
-    const double OmP = (C1P == 2 || (C1P == 0 && P.c1_power == 2)) ? Om2 : Om;
-    const double t2T = t2 * T;
-    const double C1 = fma(Q, OmP, -(e[10] * t2T));
-    const double C2 = fma(Om2, Om2, -(e[11] * t2));
-    const double C3 = fma(D, fma(e[4], t1, e[12]), fma(Q, Q, -((e[13] * t2T) * T)));
-    if (TRACK) { st.add(2, C3 * D); }   // F = r D / C3 changes sign where C3 does
+    const Num Om = w - e[0];
+    const Num Om2 = Om * Om;
+    const Num t1 = Om2 - e[1];
+    const Num t2 = Om2 - e[2];
+    if (TRACK) { st.add(0, val(t1)); st.add(1, val(t2)); }
+    const Num D = c[3] * t1 * t2;
+    const Num Q = fma(Om, e[7], fma(Om2, c[6], -(t1 * c[5])));
+    const Num T = fma(c[9], Om, e[8]);
+    const Num OmP = (C1P == 2 || (C1P == 0 && P.c1_power == 2)) ? Om2 : Om;
+    const Num t2T = t2 * T;
+    const Num C1 = fma(Q, OmP, -(c[10] * t2T));
+    const Num C2 = fma(Om2, Om2, -(e[11] * t2));
+    const Num C3 = fma(D, fma(c[4], t1, c[12]), fma(Q, Q, -((c[13] * t2T) * T)));
+    if (TRACK) { st.add(2, val(C3 * D)); }   // F = r D / C3 changes sign where C3 does
     C.n11 = -C1;                                         // all four entries /den
     C.n22 = C1;
-    C.n12 = C3 * e[15];
-    C.n21 = -(e[14] * C2);
+    C.n12 = C3 * c[15];
+    C.n21 = -(c[14] * C2);
     C.den = D;
   } else if (FAM == FAM_SLABD) {
-    const double w2 = w * w;
-    const double n1 = e[0] - w2;                         // k^2 c^2 - w^2
-    const double n2 = e[1] - w2;                         // k^2 cT^2 - w^2
-    const double n3 = e[2] - w2;                         // k^2 vA^2 - w^2
-    if (TRACK) { st.add(0, n1); st.add(1, n2); st.add(2, n3); }
-    C.n11 = 0.0; C.n22 = 0.0;
+    const Num w2 = w * w;
+    const Num n1 = e[0] - w2;                            // k^2 c^2 - w^2
+    const Num n2 = e[1] - w2;                            // k^2 cT^2 - w^2
+    const Num n3 = e[2] - w2;                            // k^2 vA^2 - w^2
+    if (TRACK) { st.add(0, val(n1)); st.add(1, val(n2)); st.add(2, val(n3)); }
+    C.n11 = Num(0.0); C.n22 = Num(0.0);
     C.n12 = n1;                                          // 1/F = n1 / (rho S n2)      /den
-    C.n21 = e[4] * n3;                                   // F m0
-    C.den = e[3] * n2;
+    C.n21 = c[4] * n3;                                   // F m0
+    C.den = c[3] * n2;
   } else {
     // m0, D and coeff of SF-G:416-427 over the common denominator den = S t Om^2 n1 (t = Om^2 - k^2 cT^2,
     // n1 = k^2 c^2 - Om^2, n3 = k^2 vA^2 - Om^2, G = S t^2 + k^4 cT^2 c^2):
     //   m0 = -n1 n3 / (S t),   D = -2 k U' G Om / den,   coeff = (k U'' S t Om n1 - 2 (k U')^2 G + n1^2 n3 Om^2) / den
-    const double Om = w - e[0];
-    const double Om2 = Om * Om;
-    const double t = Om2 - s.kcT2;
-    const double n1 = s.kc2 - Om2;
-    const double n3 = s.kvA2 - Om2;
-    if (TRACK) { st.add(0, n1); st.add(1, t); st.add(2, n3); st.add(3, Om); }
-    const double St = P.S_i * t;
-    const double G = fma(St, t, s.k4c);
-    const double X = Om * n1;
-    const double OX = Om * X;                            // n1 Om^2: shared by the numerator of coeff and the denominator
-    const double g2 = e[3] * G;                          // 2 k U' G
-    C.n11 = 0.0;
-    C.n12 = 1.0;
+    const Num Om = w - e[0];
+    const Num Om2 = Om * Om;
+    const Num t = Om2 - s.kcT2;
+    const Num n1 = s.kc2 - Om2;
+    const Num n3 = s.kvA2 - Om2;
+    if (TRACK) { st.add(0, val(n1)); st.add(1, val(t)); st.add(2, val(n3)); st.add(3, val(Om)); }
+    const Num St = P.S_i * t;
+    const Num G = fma(St, t, s.k4c);
+    const Num X = Om * n1;
+    const Num OX = Om * X;                               // n1 Om^2: shared by the numerator of coeff and the denominator
+    const Num g2 = e[3] * G;                             // 2 k U' G
+    C.n11 = Num(0.0);
+    C.n12 = Num(1.0);
     C.n22 = g2 * Om;                                     // -D                          /den
     C.n21 = -fma(e[2], St * X, fma(-g2, e[1], (n1 * n3) * OX));         // -coeff       /den
     C.den = St * OX;
   }
 }
 
-template <int FAM>
-__device__ __forceinline__ void coef_finish(const CoefPre& C, double inv, Coef& A) {
+template <int FAM, bool TRACK = true, int C1P = 0>
+__device__ __forceinline__ void coef_pre(const double* e, const ShootDev& P, const KScal& s, double w, CoefPre& C,
+                                         SignTrack& st) {
+  coef_pre<FAM, TRACK, C1P>(e, e, P, s, w, C, st);
+}
+
+template <int FAM, class Num>
+__device__ __forceinline__ void coef_finish(const CoefPreT<Num>& C, Num inv, CoefT<Num>& A) {
   if (FAM == FAM_CYL0) {
-    A.a11 = 0.0; A.a22 = 0.0; A.a12 = C.n12; A.a21 = fma(C.n21, inv, C.n22);
+    A.a11 = Num(0.0); A.a22 = Num(0.0); A.a12 = C.n12; A.a21 = fma(C.n21, inv, C.n22);
   } else if (FAM == FAM_CYLT) {
     // n11 = -n22: a11 = (-C1) inv = -(C1 inv) bit for bit -- one product, the negation rides on the source modifier of
     // the fma that uses it
     A.a22 = C.n22 * inv; A.a11 = -A.a22; A.a12 = C.n12 * inv; A.a21 = C.n21 * inv;
   } else if (FAM == FAM_SLABD) {
-    A.a11 = 0.0; A.a22 = 0.0; A.a12 = C.n12 * inv; A.a21 = C.n21;
+    A.a11 = Num(0.0); A.a22 = Num(0.0); A.a12 = C.n12 * inv; A.a21 = C.n21;
   } else {
-    A.a11 = 0.0; A.a12 = 1.0; A.a21 = C.n21 * inv; A.a22 = C.n22 * inv;
+    A.a11 = Num(0.0); A.a12 = Num(1.0); A.a21 = C.n21 * inv; A.a22 = C.n22 * inv;
   }
 }
 
 // single node (first node of a traversal): its own division
+template <int FAM, bool TRACK = true, int C1P = 0, class Num>
+__device__ __forceinline__ void coefficients(const Num* e, const double* c, const ShootDev& P, const KScalT<Num>& s,
+                                             Num w, CoefT<Num>& A, SignTrack& st) {
+  CoefPreT<Num> C;
+  coef_pre<FAM, TRACK, C1P>(e, c, P, s, w, C, st);
+  coef_finish<FAM>(C, 1.0 / C.den, A);
+}
+
 template <int FAM, bool TRACK = true, int C1P = 0>
 __device__ __forceinline__ void coefficients(const double* e, const ShootDev& P, const KScal& s, double w,
                                              Coef& A, SignTrack& st) {
-  CoefPre C;
-  coef_pre<FAM, TRACK, C1P>(e, P, s, w, C, st);
-  coef_finish<FAM>(C, 1.0 / C.den, A);
+  coefficients<FAM, TRACK, C1P>(e, e, P, s, w, A, st);
 }
 
 // Reciprocal for the hot loop: hardware seed r0 (v_rcp_f64, relative error e ~ 2^-23 at worst) and ONE third-order
@@ -308,15 +346,22 @@ __device__ __forceinline__ double fast_rcp(double x) {
 }
 
 // two nodes of one RK4 step (mid-point, end-point) with one division
+template <int FAM, bool TRACK = true, int C1P = 0, class Num>
+__device__ __forceinline__ void coefficients2(const Num* em, const double* cm, const Num* e1, const double* c1,
+                                              const ShootDev& P, const KScalT<Num>& s, Num w, CoefT<Num>& Am,
+                                              CoefT<Num>& A1, SignTrack& st) {
+  CoefPreT<Num> Cm, C1;
+  coef_pre<FAM, TRACK, C1P>(em, cm, P, s, w, Cm, st);
+  coef_pre<FAM, TRACK, C1P>(e1, c1, P, s, w, C1, st);
+  const Num inv = fast_rcp(Cm.den * C1.den);
+  coef_finish<FAM>(Cm, C1.den * inv, Am);
+  coef_finish<FAM>(C1, Cm.den * inv, A1);
+}
+
 template <int FAM, bool TRACK = true, int C1P = 0>
 __device__ __forceinline__ void coefficients2(const double* em, const double* e1, const ShootDev& P,
                                               const KScal& s, double w, Coef& Am, Coef& A1, SignTrack& st) {
-  CoefPre Cm, C1;
-  coef_pre<FAM, TRACK, C1P>(em, P, s, w, Cm, st);
-  coef_pre<FAM, TRACK, C1P>(e1, P, s, w, C1, st);
-  const double inv = fast_rcp(Cm.den * C1.den);
-  coef_finish<FAM>(Cm, C1.den * inv, Am);
-  coef_finish<FAM>(C1, Cm.den * inv, A1);
+  coefficients2<FAM, TRACK, C1P>(em, em, e1, e1, P, s, w, Am, A1, st);
 }
 
 // four nodes of TWO consecutive RK4 steps (mid-point and end-point of each) with one division: the product tree
@@ -359,14 +404,14 @@ __device__ __forceinline__ void coefficients4(const double* em, const double* e1
 // transposed system taken through the stages in reverse order (A_{j+1}^T, A_{j+1/2}^T, A_j^T), same h.  So the
 // row  r = r_end^T T  is obtained by ONE vector z = (p, q) marched from the far end back to the boundary:
 //      z <- M_j^T z ,   rhs(z) = A^T z = (a11 p + a21 q, a12 p + a22 q).
-template <int SHAPE>
-__device__ __forceinline__ void rk4_step_adjoint(double& p, double& q, const Coef& B0, const Coef& Bm, const Coef& B1,
-                                                 double h, double h2, double h6, double h3) {
+template <int SHAPE, class Num>
+__device__ __forceinline__ void rk4_step_adjoint(Num& p, Num& q, const CoefT<Num>& B0, const CoefT<Num>& Bm,
+                                                 const CoefT<Num>& B1, double h, double h2, double h6, double h3) {
 #define ES_RHS_T(A, pp, qq, kp, kq)                                                          \
   if (SHAPE == 1)      { kp = fma(-A.a22, pp, A.a21 * qq); kq = fma(A.a22, qq, A.a12 * pp); } /* a11 = -a22 */ \
   else if (SHAPE == 2) { kp = A.a21 * qq;                 kq = fma(A.a22, qq, pp); }         \
   else                 { kp = A.a21 * qq;                 kq = A.a12 * pp; }
-  double k1p, k1q, k2p, k2q, k3p, k3q, k4p, k4q, tp, tq;
+  Num k1p, k1q, k2p, k2q, k3p, k3q, k4p, k4q, tp, tq;
   ES_RHS_T(B0, p, q, k1p, k1q);
   tp = fma(h2, k1p, p); tq = fma(h2, k1q, q);
   ES_RHS_T(Bm, tp, tq, k2p, k2q);
@@ -383,14 +428,15 @@ __device__ __forceinline__ void rk4_step_adjoint(double& p, double& q, const Coe
 // with t1 = z + A0^T z, t2 = z + Am^T t1, t3 = z + 2 Am^T t2 (the three stage arguments) the classical combination
 // z + h/6 (k1 + 2 k2 + 2 k3 + k4) equals (t1 + 2 t2 + t3 - z + A1^T t3) / 3 -- 18 instructions instead of 22, and no
 // separate products with the step size.  Mathematically the step of rk4_step_adjoint<0>; rounding differs.
-__device__ __forceinline__ void rk4_step_adjoint_scaled0(double& p, double& q, const Coef& B0, const Coef& Bm,
-                                                         const Coef& B1) {
-  const double tp1 = fma(B0.a21, q, p),   tq1 = fma(B0.a12, p, q);
-  const double tp2 = fma(Bm.a21, tq1, p), tq2 = fma(Bm.a12, tp1, q);
-  const double am2 = Bm.a21 + Bm.a21,     bm2 = Bm.a12 + Bm.a12;
-  const double tp3 = fma(am2, tq2, p),    tq3 = fma(bm2, tp2, q);
-  const double sp = fma(2.0, tp2, tp1 + tp3) - p;
-  const double sq = fma(2.0, tq2, tq1 + tq3) - q;
+template <class Num>
+__device__ __forceinline__ void rk4_step_adjoint_scaled0(Num& p, Num& q, const CoefT<Num>& B0, const CoefT<Num>& Bm,
+                                                         const CoefT<Num>& B1) {
+  const Num tp1 = fma(B0.a21, q, p),   tq1 = fma(B0.a12, p, q);
+  const Num tp2 = fma(Bm.a21, tq1, p), tq2 = fma(Bm.a12, tp1, q);
+  const Num am2 = Bm.a21 + Bm.a21,     bm2 = Bm.a12 + Bm.a12;
+  const Num tp3 = fma(am2, tq2, p),    tq3 = fma(bm2, tp2, q);
+  const Num sp = fma(2.0, tp2, tp1 + tp3) - p;
+  const Num sq = fma(2.0, tq2, tq1 + tq3) - q;
   constexpr double third = 1.0 / 3.0;
   p = fma(B1.a21, tq3, sp) * third;
   q = fma(B1.a12, tp3, sq) * third;
@@ -402,15 +448,16 @@ __device__ __forceinline__ void rk4_step_adjoint_scaled0(double& p, double& q, c
 // instead of 18.  z then grows by 3 per step and is brought back by an exact power of two at the end of every LDS
 // chunk, chosen from the number of steps marched so far so that the accumulated factor 3^s 2^-floor(s log2 3) stays in
 // [1, 2) whatever the node count: adjoint_rescale(s_before, s_after) = 2^-(floor(s_after log2 3) - floor(s_before log2 3)).
-__device__ __forceinline__ void rk4_step_adjoint_scaled0_x3(double& p, double& q, const Coef& B0, const Coef& Bm,
-                                                            const Coef& B1) {
-  const double tp1 = fma(B0.a21, q, p),   tq1 = fma(B0.a12, p, q);
-  const double tp2 = fma(Bm.a21, tq1, p), tq2 = fma(Bm.a12, tp1, q);
-  const double am2 = Bm.a21 + Bm.a21,     bm2 = Bm.a12 + Bm.a12;
-  const double tp3 = fma(am2, tq2, p),    tq3 = fma(bm2, tp2, q);
+template <class Num>
+__device__ __forceinline__ void rk4_step_adjoint_scaled0_x3(Num& p, Num& q, const CoefT<Num>& B0, const CoefT<Num>& Bm,
+                                                            const CoefT<Num>& B1) {
+  const Num tp1 = fma(B0.a21, q, p),   tq1 = fma(B0.a12, p, q);
+  const Num tp2 = fma(Bm.a21, tq1, p), tq2 = fma(Bm.a12, tp1, q);
+  const Num am2 = Bm.a21 + Bm.a21,     bm2 = Bm.a12 + Bm.a12;
+  const Num tp3 = fma(am2, tq2, p),    tq3 = fma(bm2, tp2, q);
   // t1 + 2 t2 + (t3 - z) with t3 - z = 2 Am^T t2 taken as the product it is: two fmas per component instead of add, fma, sub
-  const double sp = fma(am2, tq2, fma(2.0, tp2, tp1));
-  const double sq = fma(bm2, tp2, fma(2.0, tq2, tq1));
+  const Num sp = fma(am2, tq2, fma(2.0, tp2, tp1));
+  const Num sq = fma(bm2, tp2, fma(2.0, tq2, tq1));
   p = fma(B1.a21, tq3, sp);
   q = fma(B1.a12, tp3, sq);
 }
@@ -422,8 +469,8 @@ __host__ __device__ inline int adjoint_rescale_exp(int s_before, int s_after) {
   return (int)((double)s_before * 1.5849625007211561) - (int)((double)s_after * 1.5849625007211561);
 }
 
-template <int FAM>
-__device__ __forceinline__ void adjoint_rescale(double& p, double& q, int s_before, int s_after) {
+template <int FAM, class Num>
+__device__ __forceinline__ void adjoint_rescale(Num& p, Num& q, int s_before, int s_after) {
   if (fam_unnormalised<FAM>()) {
     const int ex = adjoint_rescale_exp(s_before, s_after);
     p = ldexp(p, ex);
@@ -431,8 +478,8 @@ __device__ __forceinline__ void adjoint_rescale(double& p, double& q, int s_befo
   }
 }
 
-template <int FAM>
-__device__ __forceinline__ void adjoint_step(double& p, double& q, const Coef& B0, const Coef& Bm, const Coef& B1,
+template <int FAM, class Num>
+__device__ __forceinline__ void adjoint_step(Num& p, Num& q, const CoefT<Num>& B0, const CoefT<Num>& Bm, const CoefT<Num>& B1,
                                              double h, double h2, double h6, double h3) {
   if (fam_unnormalised<FAM>()) rk4_step_adjoint_scaled0_x3(p, q, B0, Bm, B1);
   else if (fam_scaled<FAM>()) rk4_step_adjoint_scaled0(p, q, B0, Bm, B1);
@@ -448,117 +495,126 @@ __device__ __forceinline__ void adjoint_step_normalised(double& p, double& q, co
 }
 
 // start vector of the adjoint march: the functional the far-end condition applies to (u, v)
-__device__ __forceinline__ void adjoint_start(const ShootDev& P, const Coef& A_last, double& p, double& q) {
-  if ((P.family == FAM_CYL0 || P.family == FAM_CYLT) && P.axis_bc == ES_AXIS_SAUSAGE) {
+// FAM: the family where the kernel knows it at compile time, -1: the problem's
+template <int FAM = -1, class Num>
+__device__ __forceinline__ void adjoint_start(const ShootDev& P, const CoefT<Num>& A_last, Num& p, Num& q) {
+  const int fam = (FAM < 0) ? P.family : FAM;
+  if ((fam == FAM_CYL0 || fam == FAM_CYLT) && P.axis_bc == ES_AXIS_SAUSAGE) {
     p = A_last.a11; q = A_last.a12;        // P'(r_ax) = a11 P + a12 Xi = 0   (CD-C:1082-1085)
   } else {
-    p = 1.0; q = 0.0;                      // P(r_ax) = target (kink) ; Vx(+1) = -/+ Vx(-1) (slabs)
+    p = Num(1.0); q = Num(0.0);            // P(r_ax) = target (kink) ; Vx(+1) = -/+ Vx(-1) (slabs)
   }
 }
 
 // ---- exterior ------------------------------------------------------------------------------------------------
-struct Exterior {
-  double m_e;       // reference's m_e
-  double cst;       // xi_e_const (cylinder) or p_e_const (slab)
-  double yb, dyb;   // exterior solution and its derivative at the boundary, scaled to |yb| = 1 (sign kept)
-  double Oe;        // Doppler-shifted exterior frequency (slab)
+template <class Num> struct ExteriorT {
+  Num m_e;          // reference's m_e
+  Num cst;          // xi_e_const (cylinder) or p_e_const (slab)
+  double yb;        // exterior solution at the boundary, scaled to |yb| = 1 (sign kept): +-1, a constant of the differentiation
+  Num dyb;          // its derivative at the boundary, same scale
+  Num Oe;           // Doppler-shifted exterior frequency (slab)
   int status;       // ES_PT_OK / LEAKY / NONFINITE
 };
+using Exterior = ExteriorT<double>;
 
 // w_cst: frequency at which xi_e_const is evaluated (= w everywhere except inside CR-SF's locate_sausage, which reads
 // the enclosing loop's stale value)
-__device__ __forceinline__ Exterior exterior_cylinder(const ShootDev& P, double k, double w, double w_cst) {
-  Exterior X;
-  const double k2 = k * k, w2 = w * w;
+template <class Num>
+__device__ __forceinline__ ExteriorT<Num> exterior_cylinder(const ShootDev& P, Num k, Num w, Num w_cst) {
+  using esb::ke_pair;
+  using esb::ie_pair_from_k;
+  ExteriorT<Num> X;
+  const Num k2 = k * k, w2 = w * w;
   X.Oe = w;
   X.m_e = ((k2 * P.vAe2 - w2) * (k2 * P.ce2 - w2)) / (P.Se * (k2 * P.cTe2 - w2));     // CF:699
   X.cst = -1.0 / (P.rho_e * (k2 * P.vAe2 - w_cst * w_cst));                          // CF:702
-  X.yb = X.dyb = NAN;
-  if (X.m_e < 0.0) { X.status = ES_PT_LEAKY; return X; }
-  if (!(X.m_e > 0.0) || !isfinite(X.m_e) || !isfinite(X.cst)) { X.status = ES_PT_NONFINITE; return X; }
+  X.dyb = Num(NAN); X.yb = NAN;
+  if (val(X.m_e) < 0.0) { X.status = ES_PT_LEAKY; return X; }
+  if (!(val(X.m_e) > 0.0) || !isfinite(val(X.m_e)) || !isfinite(val(X.cst))) { X.status = ES_PT_NONFINITE; return X; }
   X.status = ES_PT_OK;
-  const double mu = sqrt(X.m_e);
+  const Num mu = sqrt(X.m_e);
   const double sgn = (P.xb < 0.0) ? -1.0 : 1.0;
-  const double xR = mu * (P.R_factor / k), xb = mu;
+  const Num xR = mu * (P.R_factor / k), xb = mu;
   const int n = P.m_ext;
-  double Kb, Kb1, KR, KR1;
-  esb::ke_pair(n, xb, Kb, Kb1);
-  esb::ke_pair(n, xR, KR, KR1);
+  Num Kb, Kb1, KR, KR1;
+  ke_pair(n, xb, Kb, Kb1);
+  ke_pair(n, xR, KR, KR1);
   const double dn = (double)n;
-  const double dKb = -Kb1 + (dn / xb) * Kb;          // e^x K_n'(x)
-  const double dKR = -KR1 + (dn / xR) * KR;
-  const double g = P.ic1 / (sgn * mu);
+  const Num dKb = -Kb1 + (dn / xb) * Kb;             // e^x K_n'(x)
+  const Num dKR = -KR1 + (dn / xR) * KR;
+  const Num g = P.ic1 / (sgn * mu);
   // P = a I + b K with (a, b) from the far-field values; common positive factor xR e^{xR - xb} dropped
-  double Pv, dPv;
-  const double gap = xR - xb;
-  if (gap < 40.0) {
-    double Ib, Ib1, IR, IR1;
-    esb::ie_pair_from_k(n, xb, Kb, Kb1, Ib, Ib1);
-    esb::ie_pair_from_k(n, xR, KR, KR1, IR, IR1);
-    const double dIb = Ib1 + (dn / xb) * Ib;         // e^-x I_n'(x)
-    const double dIR = IR1 + (dn / xR) * IR;
-    const double a_s = -(P.ic0 * dKR - g * KR);
-    const double b_s = -(g * IR - P.ic0 * dIR);
-    const double E2 = exp(-2.0 * gap);
+  Num Pv, dPv;
+  const Num gap = xR - xb;
+  if (val(gap) < 40.0) {
+    Num Ib, Ib1, IR, IR1;
+    ie_pair_from_k(n, xb, Kb, Kb1, Ib, Ib1);
+    ie_pair_from_k(n, xR, KR, KR1, IR, IR1);
+    const Num dIb = Ib1 + (dn / xb) * Ib;            // e^-x I_n'(x)
+    const Num dIR = IR1 + (dn / xR) * IR;
+    const Num a_s = -(P.ic0 * dKR - g * KR);
+    const Num b_s = -(g * IR - P.ic0 * dIR);
+    const Num E2 = exp(-2.0 * gap);
     Pv = b_s * Kb + E2 * a_s * Ib;
     dPv = sgn * mu * (b_s * dKb + E2 * a_s * dIb);
   } else {
     // I-admixture below 1e-34: b ~ (ic0 - g) up to a positive factor (I' ~ I at large argument is NOT assumed:
     // the sign of b only needs g I - ic0 I', evaluated with the leading asymptotic ratio I'/I = 1 - (1/2x) ...)
-    double IR, IR1;
     // ratio I_n'/I_n at xR from the uniform large-argument expansion is not needed to machine precision here:
-    // only sign(b) enters (the K-part is normalised away).  Use I'/I = 1 - 1/(2x) - (4n^2-1)/(8x^2).
-    const double rI = 1.0 - 0.5 / xR - (4.0 * dn * dn - 1.0) / (8.0 * xR * xR);
-    (void)IR; (void)IR1;
-    const double b_s = -(g - P.ic0 * rI);
+    // only sign(b) enters (the K-part is normalised away): b_s is a constant of the differentiation.
+    // Use I'/I = 1 - 1/(2x) - (4n^2-1)/(8x^2).
+    const double rI = 1.0 - 0.5 / val(xR) - (4.0 * dn * dn - 1.0) / (8.0 * val(xR) * val(xR));
+    const double b_s = -(val(g) - P.ic0 * rI);
     Pv = b_s * Kb;
     dPv = sgn * mu * (b_s * dKb);
   }
-  const double nrm = fabs(Pv);
-  X.yb = Pv / nrm;
+  const Num nrm = fabs(Pv);                          // differentiates as sign(P_v) dP_v
+  X.yb = val(Pv) / val(nrm);
   X.dyb = dPv / nrm;
-  if (!isfinite(X.yb) || !isfinite(X.dyb)) X.status = ES_PT_NONFINITE;
+  if (!isfinite(X.yb) || !isfinite(val(X.dyb))) X.status = ES_PT_NONFINITE;
   return X;
 }
 
-__device__ __forceinline__ Exterior exterior_slab(const ShootDev& P, double k, double w) {
-  Exterior X;
-  const double k2 = k * k;
-  const double Oe = w - k * P.U_e;
-  const double Oe2 = Oe * Oe;
+template <class Num>
+__device__ __forceinline__ ExteriorT<Num> exterior_slab(const ShootDev& P, Num k, Num w) {
+  ExteriorT<Num> X;
+  const Num k2 = k * k;
+  const Num Oe = w - k * P.U_e;
+  const Num Oe2 = Oe * Oe;
   X.Oe = Oe;
   X.m_e = ((k2 * P.vAe2 - Oe2) * (k2 * P.ce2 - Oe2)) / (P.Se * (k2 * P.cTe2 - Oe2));          // SF-U:542
   X.cst = P.rho_e * P.Se * (k2 * P.cTe2 - Oe2) / (Oe * (k2 * P.ce2 - Oe2));                   // SF-U:545
-  X.yb = X.dyb = NAN;
-  if (X.m_e < 0.0) { X.status = ES_PT_LEAKY; return X; }
-  if (!(X.m_e > 0.0) || !isfinite(X.m_e) || !isfinite(X.cst)) { X.status = ES_PT_NONFINITE; return X; }
+  X.dyb = Num(NAN); X.yb = NAN;
+  if (val(X.m_e) < 0.0) { X.status = ES_PT_LEAKY; return X; }
+  if (!(val(X.m_e) > 0.0) || !isfinite(val(X.m_e)) || !isfinite(val(X.cst))) { X.status = ES_PT_NONFINITE; return X; }
   X.status = ES_PT_OK;
-  const double mu = sqrt(X.m_e);
-  const double R = P.R_factor / k;
-  const double E2 = exp(-2.0 * mu * (R - 1.0));
-  const double gp = P.ic0 + P.ic1 / mu, gm = P.ic0 - P.ic1 / mu;
-  const double V = gp + E2 * gm;
-  const double dV = mu * (gp - E2 * gm);
-  const double nrm = fabs(V);
-  X.yb = V / nrm;
+  const Num mu = sqrt(X.m_e);
+  const Num R = P.R_factor / k;
+  const Num E2 = exp(-2.0 * mu * (R - 1.0));
+  const Num gp = P.ic0 + P.ic1 / mu, gm = P.ic0 - P.ic1 / mu;
+  const Num V = gp + E2 * gm;
+  const Num dV = mu * (gp - E2 * gm);
+  const Num nrm = fabs(V);
+  X.yb = val(V) / val(nrm);
   X.dyb = dV / nrm;
-  if (!isfinite(X.yb) || !isfinite(X.dyb)) X.status = ES_PT_NONFINITE;
+  if (!isfinite(X.yb) || !isfinite(val(X.dyb))) X.status = ES_PT_NONFINITE;
   return X;
 }
 
 // ---- boundary algebra ------------------------------------------------------------------------------------------
 // Inputs: the row r = (r1, r2) of the transfer matrix selected by the far-end condition (r . (u_b, v_b) = target),
 // the node entries of the first node and the exterior (outer = cst * dyb, yb, Oe).  Output: mismatch d = outer - inner.
-struct Mismatch { double d, outer, inner; };
+template <class Num> struct MismatchT { Num d, outer, inner; };
+using Mismatch = MismatchT<double>;
 
-template <int FAM, class Ext>
-__device__ __forceinline__ Mismatch boundary_algebra(const ShootDev& P, const KScal& s, double w, const Ext& X,
-                                                     double r1, double r2, const double* e_first) {
-  Mismatch M;
+template <int FAM, class Num, class Ext>
+__device__ __forceinline__ MismatchT<Num> boundary_algebra(const ShootDev& P, const KScalT<Num>& s, Num w, const Ext& X, Num r1,
+                                                           Num r2, const Num* e_first) {
+  MismatchT<Num> M;
   if (FAM == FAM_CYL0 || FAM == FAM_CYLT) {
     const double Pb = X.yb;
-    const double xi_e = X.outer;                                        // left_xi_solution[-1], CF:775
-    double Xb;
+    const Num xi_e = X.outer;                                           // left_xi_solution[-1], CF:775
+    Num Xb;
     if (P.axis_bc == ES_AXIS_KINK) {
       Xb = (P.bc_const * xi_e - r1 * Pb) / r2;                          // P(r_ax) = B_phi(-1)^2 xi_e, CF:795
     } else if (P.axis_bc == ES_AXIS_ROTATION_KINK) {
@@ -566,20 +622,20 @@ __device__ __forceinline__ Mismatch boundary_algebra(const ShootDev& P, const KS
     } else {
       Xb = -(r1 * Pb) / r2;                                             // P'(r_ax) = 0, CD-C:1082-1085
     }
-    const double xi_i = Xb / P.xb;                                      // inside_xi_solution[0], CF:798
+    const Num xi_i = Xb / P.xb;                                         // inside_xi_solution[0], CF:798
     M.outer = xi_e; M.inner = xi_i; M.d = xi_e - xi_i;
   } else {
-    const double P_left = X.outer;                                      // left_P_solution[-1], SF-U:559
+    const Num P_left = X.outer;                                         // left_P_solution[-1], SF-U:559
     if (FAM == FAM_SLABD) {
       const double Vb = X.yb;                                           // SD-P:473
-      const double sv = (P.slab_sign - r1) * Vb / r2;                   // v(-1) = F Vx'(-1)
+      const Num sv = (P.slab_sign - r1) * Vb / r2;                      // v(-1) = F Vx'(-1)
       M.inner = sv / w;                                                 // P_Ti Vx' = (F/w)(sv/F), SD-P:346,495
     } else {
-      const double Omb = w - e_first[0];                                // w - k U_i(-1)
-      const double Vb = X.yb * Omb / X.Oe;                              // SF-U:558
-      const double sv = (P.slab_sign - r1) * Vb / r2;                   // Vx'(-1)
-      const double Omb2 = Omb * Omb;
-      const double PTi = P.rho_i * P.S_i * (s.kcT2 - Omb2) / (Omb * (s.kc2 - Omb2));   // SF-G:433
+      const Num Omb = w - e_first[0];                                   // w - k U_i(-1)
+      const Num Vb = X.yb * Omb / X.Oe;                                 // SF-U:558
+      const Num sv = (P.slab_sign - r1) * Vb / r2;                      // Vx'(-1)
+      const Num Omb2 = Omb * Omb;
+      const Num PTi = P.rho_i * P.S_i * (s.kcT2 - Omb2) / (Omb * (s.kc2 - Omb2));   // SF-G:433
       M.inner = PTi * sv;
     }
     M.outer = P_left;

@@ -46,16 +46,22 @@ __device__ __forceinline__ double pick_w(const double* __restrict__ wv, int w_mo
 
 // What the boundary algebra needs from the exterior: outer = cst * dyb (xi_e resp. P_left), the normalised boundary
 // value yb (+-1), the Doppler-shifted exterior frequency (flow slab) and the status.
-struct ExteriorLite {
-  double outer, yb, Oe;
+template <class Num> struct ExteriorLiteT {
+  Num outer;
+  double yb;
+  Num Oe;
   int status;
 };
+using ExteriorLite = ExteriorLiteT<double>;
 
 // Evaluated BEFORE the RK4 march (few live registers), inlined: the Bessel series / continued fraction need ~100
 // VGPRs of their own, which then overlap with nothing; only the three results are carried through the loop.
-__device__ __forceinline__ ExteriorLite exterior_lite(const ShootDev& P, double k, double w, double w_cst) {
-  const Exterior X = (P.family == FAM_CYL0 || P.family == FAM_CYLT) ? exterior_cylinder(P, k, w, w_cst) : exterior_slab(P, k, w);
-  ExteriorLite L;
+// FAM: the family where the kernel knows it at compile time (only its exterior is then instantiated), -1: the problem's.
+template <int FAM = -1, class Num>
+__device__ __forceinline__ ExteriorLiteT<Num> exterior_lite(const ShootDev& P, Num k, Num w, Num w_cst) {
+  const int fam = (FAM < 0) ? P.family : FAM;
+  const ExteriorT<Num> X = (fam == FAM_CYL0 || fam == FAM_CYLT) ? exterior_cylinder(P, k, w, w_cst) : exterior_slab(P, k, w);
+  ExteriorLiteT<Num> L;
   L.outer = X.cst * X.dyb;
   L.yb = X.yb;
   L.Oe = X.Oe;

@@ -69,12 +69,14 @@ SMALL_N = (130, 2, 3)
 @functools.lru_cache(maxsize=None)
 def all_cases():
     """tests/cases.py plus one m = 5 cylinder, the four large-gap problems (far field at 10 wavelengths), a cylinder with a
-    non-zero axis target and short grids (N = 130: three workgroups' worth of pairs stay cheap; N = 2, 3: one and two steps)."""
+    non-zero axis target and short grids (N = 130: three workgroups' worth of pairs stay cheap; N = 2, 3: one and two steps; the
+    density slab at N = 2)."""
     c = dict(cases.all_cases())
     c["CF_flow_kink_target"] = (FlowWithAxisTarget(U_i0=0.6, width=1.0), "kink", None, (2.7, 4.95))
     for N in SMALL_N:
         c[f"CF_flow_kink_N{N}"] = (q.CylinderFlow(U_i0=0.6, width=1.0, n_nodes=N), "kink", None, (2.7, 4.95))
         c[f"SFG_flow_kink_N{N}"] = (q.SlabFlow(U_i0=0.35, width=1.5, n_nodes=N), "kink", None, (1.4, 2.45))
+    c["SD_w15_sausage_N2"] = (q.SlabDensity(width=1.5, n_nodes=2), "sausage", None, (0.9, 1.25))
     c["CF_flow_m5"] = (q.CylinderFlow(U_i0=0.35, width=0.9), "kink", 5, (2.7, 4.95))
     c["LG_flow_kink"] = (q.CylinderFlow(U_i0=0.6, width=1.0, L_factor=10.0), "kink", None, (2.7, 4.95))
     c["LG_flow_sausage"] = (q.CylinderFlow(U_i0=0.6, width=1.0, L_factor=10.0), "sausage", None, (2.7, 4.95))

@@ -90,6 +90,25 @@ def test_value_is_the_determinant_of_eval_points(pool, name):
         assert err <= 1e-12, (name, i, g["outer"][0, i], g["inner"][0, i], D[i])
 
 
+# Where the slopes march and the point march group their reciprocals alike, the two run the same operations on the same values
+# (one formula text, es_shoot_device.hpp, over jets and over doubles): the twisted cylinder at any node count (its point march
+# takes one reciprocal per step) and every family at N = 2 (a single, even top step is taken alone).
+BITWISE_CASES = tuple(n for n in R.VALUE_CASES if n.startswith("CR_")) + ("CF_flow_kink_N2", "SFG_flow_kink_N2", "SD_w15_sausage_N2")
+
+
+@pytest.mark.parametrize("name", BITWISE_CASES)
+def test_value_is_the_determinant_bit_for_bit_where_the_reciprocals_group_alike(pool, name):
+    gp = pool.problem(name)
+    k, w = R.pairs(name)
+    g = _np(gp.root_slopes(k, w))
+    D = gp.eval_points(k, w)[0].cpu().numpy()
+    assert g["status"].tolist() == [0] * len(k)
+    d = g["outer"][0] - g["inner"][0]                       # fp64 on the host: the subtraction the point kernel ends with
+    for i in range(len(k)):
+        print(f"{name} pair {i}: outer - inner = {d[i]!r}, D = {D[i]!r}, difference {d[i] - D[i]:.1e} (required: equal bits)")
+    assert np.isfinite(D).all() and np.array_equal(d, D), (name, d, D)
+
+
 def test_status_and_nan_rows(pool):
     """A leaky pair and two non-finite ones among good ones: the status is the exterior status es_shoot_mode_signature reports
     (that of es_shoot_eigenfunction, whose rows are NaN exactly there), all six entries are NaN there and the other pairs are

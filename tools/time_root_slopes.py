@@ -15,9 +15,12 @@ Before timing, D of the slopes leg is compared with D of eval_points on all n pa
 with the one the stencil gives.  One JSON line with median / min / max ms per leg over the repeats and the ratios is printed and
 appended to --out.
 
-    python tools/time_root_slopes.py [--repeats 20] [--warmup 3] [--log2n 17] [--out profiles/root_slopes_timing.jsonl]
+--lib: another build of the library (an earlier commit's, to time both in one visit in processes that take turns).
+
+    python tools/time_root_slopes.py [--repeats 20] [--warmup 3] [--log2n 17] [--lib PATH] [--out profiles/root_slopes_timing.jsonl]
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2n", type=int, default=17)
+    ap.add_argument("--lib", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "root_slopes_timing.jsonl"))
     a = ap.parse_args()
     assert a.repeats >= 10, "at least 10 timed repeats per leg"
@@ -43,7 +47,11 @@ def main():
     assert torch.cuda.is_available(), "this tool measures on the GPU; there is nothing to fall back to"
     dev = torch.device("cuda", torch.cuda.current_device())
     stream = torch.cuda.Stream(device=dev)
-    ctx = _lib.Context(dev.index or 0, stream=stream)
+    other = None
+    if a.lib:
+        other = ctypes.CDLL(a.lib)
+        _lib._sig(other)
+    ctx = _lib.Context(dev.index or 0, stream=stream, lib=other)
     n = 1 << a.log2n
     with torch.cuda.stream(stream):
         gp = ShootProblem(bench.workload_equilibrium(), "kink", ctx=ctx)
@@ -107,7 +115,7 @@ def main():
             e1.synchronize()
             if it >= a.warmup:
                 ms[name].append(e0.elapsed_time(e1))
-    line = {"device": torch.cuda.get_device_name(dev), "pairs": n, "nodes": N, "distinct_roots": n_roots, "brackets": int(cnt),
+    line = {"device": torch.cuda.get_device_name(dev), "lib": os.path.basename(a.lib) if a.lib else "default", "pairs": n, "nodes": N, "distinct_roots": n_roots, "brackets": int(cnt),
             "pairs_ok": int(ok.sum().item()), "value_vs_eval_points": value_err, "stencil_step": STEP,
             "cg_vs_stencil_median": cg_diff_median, "cg_vs_stencil_max": cg_diff_max,
             "repeats": a.repeats, "warmup": a.warmup, "legs": {}}
