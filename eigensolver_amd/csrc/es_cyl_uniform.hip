@@ -10,6 +10,7 @@
 //   exterior and mismatch exactly as in the shooting path (exterior_cylinder).
 #include "es_common.hpp"
 #include "es_shoot_device.hpp"
+#include "es_refine_rule.hpp"
 
 namespace {
 
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(256) void cyl_uniform_ends_kernel(ShootDev P, UniDe
   if (in) (e ? tab.d_resid : tab.d_w)[i] = D;
 }
 
-// The ES_REFINE_SECTION rule of refine_kernel + refine_polish_kernel (es_shoot.hip), statement for statement, with the
+// The ES_REFINE_SECTION rule (es_refine_rule.hpp, the text refine_kernel + refine_polish_kernel of es_refine.hip use) with the
 // closed form as the evaluation: 16 lanes per bracket, n_rounds rounds of 17-section steered by a wave ballot, then
 // UNI_POLISH regula-falsi steps in which the 16 lanes of a bracket evaluate the same secant point (an evaluation is a few
 // Bessel calls: two rounds in twelve at a sixteenth of their use cost less than two more launches).  One evaluation site.
@@ -213,45 +214,27 @@ __global__ __launch_bounds__(256) void cyl_uniform_refine_kernel(ShootDev P, Uni
   const bool in = i < n;
   const double k = in ? tab.d_k[i] : 1.0;
   const int m = (in && d_order) ? d_order[i] : m_first;
-  double lo = in ? tab.d_w_lo[i] : 1.0;
-  double hi = in ? tab.d_w_hi[i] : 2.0;
-  double flo = in ? tab.d_w[i] : 1.0;
-  double fhi = in ? tab.d_resid[i] : -1.0;
-  const double frac = (double)(j + 1) / (double)(UNI_LANES + 1);
+  es_bracket b = {in ? tab.d_w_lo[i] : 1.0, in ? tab.d_w_hi[i] : 2.0, in ? tab.d_w[i] : 1.0, in ? tab.d_resid[i] : -1.0};
+  const double frac = es_section_frac<UNI_LANES>(j);
   double D = 0.0, rel = 0.0; uint8_t st = 0;
-  double root = lo;
+  double root = b.lo;
   for (int it = 0; it < n_rounds + UNI_POLISH; ++it) {
     const bool section = it < n_rounds;
-    double x;
-    if (section) {
-      x = lo + (hi - lo) * frac;
-    } else {
-      x = lo - flo * (hi - lo) / (fhi - flo);
-      if (!(x > lo && x < hi)) x = (x == x) ? ((fabs(flo) <= fabs(fhi)) ? lo : hi) : lo + (hi - lo) * 0.5;
-    }
+    const double x = section ? es_section_point(b, frac) : es_secant_point(b);
     uni_point(P, U, m, m, k, x, D, rel, st);
     if (section) {
-      const bool diff = (D * flo < 0.0);               // NaN products compare false
-      const unsigned long long bal = __ballot(diff);
-      const unsigned long long bits = (bal >> (UNI_LANES * g)) & ((1ull << UNI_LANES) - 1ull);
-      const int first = bits ? (__ffsll((long long)bits) - 1) : UNI_LANES;   // first point whose sign differs from D(lo)
-      const int src_hi = g * UNI_LANES + (first < UNI_LANES ? first : UNI_LANES - 1);
-      const int src_lo = g * UNI_LANES + (first > 0 ? first - 1 : 0);
-      const double x_hi = __shfl(x, src_hi), d_hi_new = __shfl(D, src_hi);
-      const double x_lo = __shfl(x, src_lo), d_lo_new = __shfl(D, src_lo);
-      if (first < UNI_LANES) { hi = x_hi; fhi = d_hi_new; }
-      if (first > 0) { lo = x_lo; flo = (d_lo_new == d_lo_new) ? d_lo_new : flo; }
+      b = es_section_update<UNI_LANES>(b, x, D, g);
     } else {
       root = x;
-      if (D * flo < 0.0) { hi = x; fhi = D; } else if (D == D) { lo = x; flo = D; }
+      b = es_secant_update(b, x, D);
     }
   }
   if (in && j == 0) {
-    tab.d_w_lo[i] = lo;
-    tab.d_w_hi[i] = hi;
+    tab.d_w_lo[i] = b.lo;
+    tab.d_w_hi[i] = b.hi;
     tab.d_w[i] = root;
     tab.d_resid[i] = rel;
-    tab.d_flag[i] = (st == ES_PT_OK && rel < tol_percent) ? 1 : 0;
+    tab.d_flag[i] = es_accept_flag(st, rel, tol_percent);
   }
 }
 
@@ -338,9 +321,7 @@ int uniform_search_enqueue(es_context* ctx, const es_cyl_uniform_params* p, int 
                        ctx->d_block_counts, *table, d_order);
     hipLaunchKernelGGL(cyl_uniform_ends_kernel, dim3((cap + 127) / 128), dim3(256), 0, ctx->stream, S, U, *table, d_order,
                        m_first, d_n, cap);
-    // 17-section rounds equivalent to n_bisect halvings: 17^R >= 2^n_bisect (the count of launch_refine, es_shoot.hip)
-    int rounds = 0;
-    for (double span = 1.0, need = ldexp(1.0, n_bisect < 1000 ? n_bisect : 1000); span < need; span *= 17.0) ++rounds;
+    const int rounds = es_section_rounds(n_bisect, UNI_LANES + 1);      // the count of launch_refine (es_refine.hip)
     constexpr int PER_WG = 4 * (64 / UNI_LANES);
     hipLaunchKernelGGL(cyl_uniform_refine_kernel, dim3((cap + PER_WG - 1) / PER_WG), dim3(256), 0, ctx->stream, S, U,
                        *table, d_order, m_first, d_n, cap, rounds, tol_percent);

@@ -1,4 +1,6 @@
-// Shared between es_shoot.hip and es_worker.hip: problem handle and the per-lane determinant evaluation.
+// Shared between the translation units of the shooting path (es_shoot.hip, es_refine.hip, es_screen.hip, es_roots.hip,
+// es_problem.hip, es_worker.hip, ...): problem handle, tile indexing of the grid marches and the per-lane determinant
+// evaluation.
 #pragma once
 #include "es_common.hpp"
 #include "es_shoot_device.hpp"
@@ -31,6 +33,18 @@ constexpr int ES_REFINE_POLISH = 2;   // regula-falsi steps after the 9-section 
 #define ES_FAR_NODE(c_, n_) (((c_) == (n_) - 1) ? 1 : 0)
 #endif
 constexpr int CH = 128;   // RK4 steps per LDS chunk: (2*CH+1) * NE * 8 B of LDS (14.4 KiB for NE = 7)
+
+// ONE tile per workgroup, the launch has as many workgroups as tiles (es_tile_grid: the y dimension only counts beyond
+// 2^22 tiles).  The kernels are written as a loop over tiles that runs once: round 2 and most of round 3 launched at most
+// 2^22 workgroups and let each stride over the tiles -- a loop the compiler hoisted every tile-invariant value out of
+// (64-bit literals of the Bessel polynomials, kernel arguments, step sizes), and carried them in registers through the
+// march: 172 -> 103 VGPRs for the fp32 kernel of the untwisted cylinder, 286 -> 94 SGPRs spilled to lanes and no scratch
+// left in the twisted one once the loop was gone.
+constexpr long ES_TILE_GRID_X = 1L << 22;
+__device__ __forceinline__ long es_tile_index() { return (long)blockIdx.y * ES_TILE_GRID_X + blockIdx.x; }
+inline dim3 es_tile_grid(long tiles) {
+  return tiles <= ES_TILE_GRID_X ? dim3((unsigned)tiles) : dim3((unsigned)ES_TILE_GRID_X, (unsigned)((tiles + ES_TILE_GRID_X - 1) / ES_TILE_GRID_X));
+}
 
 template <int FAM>
 __device__ __forceinline__ void load_base(const ShootDev& P, int pt, double* b) {

@@ -13,7 +13,7 @@ import numpy as np
 SECTIONS = 17
 LANES = SECTIONS - 1
 POLISH = 2
-HYBRID_SECTIONS = 1          # kHybridSections of es_shoot.hip
+HYBRID_SECTIONS = 1          # kHybridSections of es_refine.hip
 ONE_LANE_STEPS = 8           # kHybridSteps
 ONE_LANE_EPS = 1e-12         # kHybridEps = ROOT_RTOL / 100
 # Early fallback on a pole signature (an iterate with |D| above |D| at both ends): NOT part of the rule.  It saves 1 - 3

@@ -42,6 +42,22 @@ def test_no_spill_inside_a_march_loop(built):
         assert f32[name].get(".vgpr_spill_count", 0) == 0, f32[name]
 
 
+def test_every_shooting_kernel_is_built_in_one_object(built):
+    """The shooting path is several translation units over shared headers: a kernel template instantiated in two of them would
+    be compiled twice and could differ between them.  107: the count of the build that had them all in es_shoot.o (102) and
+    es_cyl_uniform.o (5)."""
+    import codeobj_table
+    if os.environ.get("ES_BUILD_ALL_SHAPES") == "1":
+        pytest.skip("measuring build")
+    rows = [r for r in codeobj_table.table()
+            if r["kernel"].startswith(("shoot_", "refine_", "hybrid_", "bracket_", "unsure_", "cyl_uniform_"))]
+    where = {}
+    for r in rows:
+        where.setdefault(r["kernel"], []).append(r["object"])
+    assert not {k: v for k, v in where.items() if len(v) > 1}
+    assert len(where) == 107, len(where)
+
+
 def test_isa_loop_counts_file_is_current(built):
     _, loops = built
     committed = json.load(open(os.path.join(ROOT, "profiles", "isa_loop_counts.json")))

@@ -57,7 +57,7 @@ def test_ctypes_constants_and_signatures_match_the_header():
 
 
 def test_model_constants_are_the_kernel_s():
-    src = open(os.path.join(ROOT, "eigensolver_amd", "csrc", "es_shoot.hip")).read()
+    src = open(os.path.join(ROOT, "eigensolver_amd", "csrc", "es_refine.hip")).read()
     def const(name):
         return re.search(r"constexpr\s+\w+\s+" + name + r"\s*=\s*([0-9.eE+-]+)\s*;", src).group(1)
     assert int(const("kHybridSections")) == hm.HYBRID_SECTIONS and hm.HYBRID_SECTIONS in (1, 2)

@@ -592,6 +592,38 @@ def test_find_roots_async_is_find_roots(es_ctx, name):
     gp.close()
 
 
+@pytest.mark.parametrize("name", ["CF_flow_kink", "CR_kink"])
+def test_refinement_variants_bit_identical(es_ctx, name, monkeypatch):
+    """The forms of the section rule share one rule text (csrc/es_refine_rule.hpp) and promise the same doubles: one round /
+    one polish step per launch (the cylinder families' default) against ES_REFINE_ROUNDS_IN_KERNEL=1 (all rounds in one
+    launch), wave-shared node entries (untwisted cylinder, CHR = 32) against ES_REFINE_PRIVATE_ENTRIES=1.  131 nodes = 65
+    RK4 steps: two full chunks of 32 plus an odd top step; n_bisect = 16: four rounds and two polish steps; a bracket
+    count that is no multiple of four leaves a wave with empty groups."""
+    import dataclasses
+    from eigensolver_amd import ShootProblem
+    eq, mode, m, (lo, hi) = CASES[name]
+    gp = ShootProblem(dataclasses.replace(eq, n_nodes=131), mode, m, ctx=es_ctx)
+    k = np.array([0.7, 1.9, 3.1])
+    W = lo + (np.arange(65) + 0.5) * (hi - lo) / 65
+    D, st = gp.eval_grid(k, W)
+    tables = {}
+    for env in (None, "ES_REFINE_ROUNDS_IN_KERNEL", "ES_REFINE_PRIVATE_ENTRIES"):
+        with monkeypatch.context() as mp:
+            mp.delenv("ES_REFINE_ROUNDS_IN_KERNEL", raising=False)
+            mp.delenv("ES_REFINE_PRIVATE_ENTRIES", raising=False)
+            if env:
+                mp.setenv(env, "1")
+            roots, n = gp.find_roots(k, W, D, st, n_bisect=16, tol_percent=1e-3)
+            tables[env] = {key: roots[key].cpu().numpy().copy() for key in ("w", "w_lo", "w_hi", "resid", "flag")}
+        assert n > 0 and n % 4 != 0, (name, n)
+        assert len(tables[env]["w"]) == n
+    assert tables[None]["flag"].sum() > 0
+    for env in ("ES_REFINE_ROUNDS_IN_KERNEL", "ES_REFINE_PRIVATE_ENTRIES"):
+        for key, ref in tables[None].items():
+            assert tables[env][key].tobytes() == ref.tobytes(), (name, env, key, tables[env][key], ref)
+    gp.close()
+
+
 def test_grid_timer_counts_launches(es_ctx):
     """es_context_grid_timer / es_context_grid_time: one event pair per grid-march launch on the context's stream."""
     case = CASES["CF_flow_kink"]

@@ -10,6 +10,7 @@ rate: 16 cycles), other VALU (4), LDS reads (issued through the same port; count
 scalar / wait instructions.  bench.py prices a launch with it:  issue_cycles x (points / 64) x steps / 1024 SIMDs
 against the measured cycles of the launch (valu_issue), instead of numbers typed into the source.
 """
+import glob
 import json
 import os
 import re
@@ -153,8 +154,11 @@ def count(body, rcp_class="rcp_f64", steps_per_rcp=1):
 
 
 def table():
-    obj = os.path.join(ROOT, "eigensolver_amd", "lib", "es_shoot.o")
-    ks = kernels(disassemble(obj))
+    # the grid marches live in es_shoot.o and es_screen.o; every non-IEEE object is looked through, as codeobj_table does
+    ks = {}
+    for obj in sorted(glob.glob(os.path.join(ROOT, "eigensolver_amd", "lib", "*.o"))):
+        if not obj.endswith(".ieee.o") and codeobj_table.kernels_of(obj):      # host-only objects have no code object
+            ks.update(kernels(disassemble(obj)))
     names = list(ks)
     pretty = codeobj_table.demangle(names)
     out = {}

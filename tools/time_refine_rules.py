@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 
 WORKLOADS = ("config1", "config2", "config3", "config4", "config4/8")
 CHILD_TIMEOUT_S = 420
-SECTIONS, HYBRID_SECTIONS = 17, 1          # kRefineSections, kHybridSections of es_shoot.hip
+SECTIONS, HYBRID_SECTIONS = 17, 1          # kRefineSections, kHybridSections of es_refine.hip
 
 
 def rounds_for(n_bisect):
