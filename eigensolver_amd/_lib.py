@@ -320,4 +320,7 @@ def _sig(lib):
     # (12) slopes and Newton tracing of complex roots
     lib.es_complex_root_slopes.argtypes = [vp, vp, i, vp, vp, vp, i, vp, vp, vp, vp]
     lib.es_complex_newton.argtypes = [vp, vp, i, vp, vp, vp, i, vp, i, d, d, d, vp, vp, vp, vp, vp, vp]
+    # (13) Newton tracing of real roots
+    if hasattr(lib, "es_shoot_newton"):                     # absent from an earlier build loaded for an A/B (tools/, --lib)
+        lib.es_shoot_newton.argtypes = [vp, vp, vp, vp, i, vp, i, d, d, d, vp, vp, vp, vp, vp, vp]
     return lib

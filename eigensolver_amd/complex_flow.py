@@ -21,7 +21,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib, equilibrium as eqm
-from .shooting import ShootProblem, W_ABSOLUTE, W_PHASE_SPEED
+from .shooting import ShootProblem, W_ABSOLUTE, W_PHASE_SPEED, hermite_guess
 
 CX_SFX, CX_SFG = 0, 1
 DBL_MAX = sys.float_info.max
@@ -277,21 +277,12 @@ class SlabComplexFlow:
             raise ValueError("densify needs at least two coarse rows")
         kf = p._dev(k_fine).reshape(-1)
         s = self.root_slopes(mode, dk, wc).group_velocity
-        h = dk[1:] - dk[:-1]
-        j = torch.clamp(torch.searchsorted(dk, kf, right=True) - 1, 0, dk.numel() - 2)
-        hj = h[j]
-        t = (kf - dk[j]) / hj
-        t2, t3 = t * t, t * t * t
-        pred = ((2 * t3 - 3 * t2 + 1) * wc[j] + (t3 - 2 * t2 + t) * hj * s[j]
-                + (-2 * t3 + 3 * t2) * wc[j + 1] + (t3 - t2) * hj * s[j + 1])
+        pred, bound = hermite_guess(dk, wc, s, kf, shift_factor)
         given = newton_kw.get("max_shift") is not None
         out = self.newton(mode, kf, pred, **newton_kw)
         if given:
             out["max_shift"] = torch.full_like(kf, float(newton_kw["max_shift"]))
         else:
-            dw = wc[1:] - wc[:-1]
-            defect = torch.maximum((dw - h * s[:-1]).abs(), (dw - h * s[1:]).abs())
-            bound = torch.maximum(shift_factor * defect, 1e-8 * torch.clamp(wc[:-1].abs(), min=1.0))[j]
             out["flag"] = torch.where((out["w"] - pred).abs() <= bound, out["flag"], torch.zeros_like(out["flag"]))
             out["max_shift"] = bound
         out["k"] = kf

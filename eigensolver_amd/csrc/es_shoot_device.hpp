@@ -74,7 +74,7 @@ enum { SD_RHO = 0, SD_C2, SD_VA2 };
 enum { SF_U = 0, SF_DU, SF_DDU };
 
 // The formulas below are ONE text over a scalar type Num.  Num = double is every value kernel (and what oracle/c/shoot_port.c
-// mirrors); Num = Jet3 of es_slopes.hip carries (value, d/d omega, d/d k) through the same operations and brings its own
+// mirrors); Num = Jet<ND> of es_jet.hpp (Jet3: value, d/d omega, d/d k) goes through the same operations and brings its own
 // operators and overloads of fma, sqrt, exp, fabs, ldexp, fast_rcp, ke_pair, ie_pair_from_k and val.  val(x) is the value
 // component: what the text branches on and tracks signs of.  (Num, not T: T is a term of the twisted family's coefficients.)
 __device__ __forceinline__ double val(double x) { return x; }

@@ -106,6 +106,20 @@ def curves_with_slopes(roots, sig, slopes, accepted_only=True):
     return out
 
 
+def traced_curves(branches):
+    """The flagged points of ShootProblem.trace_branches (its `branches`, or the TracedBranches itself) in the layout of
+    curves_with_slopes: {label: (omegas, ks, cg)} with cg the dwdk of the final Newton point, each curve ordered by k --
+    ready for hermite_branch, fit_branch and, as {"kink": entry[:2]}, pickle_layout.  This is the one host read."""
+    branches = getattr(branches, "branches", branches)
+    out = {}
+    for label, b in branches.items():
+        w, k, cg = (_host(b[a]).astype(np.float64) for a in ("w", "k", "dwdk"))
+        sel = np.nonzero(_host(b["flag"]) == 1)[0]
+        sel = sel[np.argsort(k[sel], kind="stable")]
+        out[label] = (w[sel], k[sel], cg[sel])
+    return out
+
+
 def hermite_branch(ks, omegas, cg):
     """omega(k) of one branch as the piecewise-cubic Hermite interpolant through the roots (ks strictly increasing) with
     the slopes cg = d omega / dk (ShootProblem.group_velocity): what a degree-6 fit_branch stands in for when the slopes are

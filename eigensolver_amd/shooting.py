@@ -60,6 +60,48 @@ class RootSlopes(NamedTuple):
         return -self.d / self.d_w
 
 
+class TracedBranches(NamedTuple):
+    """ShootProblem.trace_branches: `branches` {label: dict of CUDA tensors k, w, dwdk, resid, iters, flag, status, predicted,
+    max_shift}, views into the tensors of the one Newton launch; `skipped` the labels that were not traced (a single row,
+    or wavenumbers that repeat: two roots of a row share the label)."""
+    branches: dict
+    skipped: list
+
+
+def _host_array(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def hermite_guess(k, w, s, k_fine, shift_factor=4.0):
+    """The prediction a Newton trace starts from, on the device, for real or complex roots: k [n] strictly increasing
+    (float64), the roots w [n] on it with their slopes s = d omega / dk, k_fine [m] -- CUDA tensors.  Returns
+    (predicted [m], bound [m]): the piecewise-cubic Hermite interpolant at k_fine (the cubic of the end interval continued
+    outside [k[0], k[-1]]) and, per fine point, the shift bound of its coarse interval [k_j, k_j+1]: shift_factor times the
+    larger of the interval's two end-point Hermite defects
+        |w_j+1 - w_j - h s_j|,  |w_j+1 - w_j - h s_j+1|      (h = k_j+1 - k_j)
+    -- how far the tangent from one end misses the root at the other, a scale for how far the curve bends inside the
+    interval and so for how far the cubic can lie from it -- and no less than 1e-8 max(1, |w_j|)."""
+    import torch
+    j = torch.clamp(torch.searchsorted(k, k_fine, right=True) - 1, 0, k.numel() - 2)
+    return hermite_guess_in(k, w, s, j, k_fine, shift_factor)
+
+
+def hermite_guess_in(k, w, s, j, k_fine, shift_factor=4.0):
+    """hermite_guess with the coarse interval [k_j, k_j+1] of every fine point given (int64 [m]): k need then be increasing
+    only inside the intervals that are used, so several branches can lie one after the other in k, w and s."""
+    import torch
+    h = k[1:] - k[:-1]
+    hj = h[j]
+    t = (k_fine - k[j]) / hj
+    t2, t3 = t * t, t * t * t
+    pred = ((2 * t3 - 3 * t2 + 1) * w[j] + (t3 - 2 * t2 + t) * hj * s[j]
+            + (-2 * t3 + 3 * t2) * w[j + 1] + (t3 - t2) * hj * s[j + 1])
+    dw = w[1:] - w[:-1]
+    defect = torch.maximum((dw - h * s[:-1]).abs(), (dw - h * s[1:]).abs())
+    bound = torch.maximum(shift_factor * defect, 1e-8 * torch.clamp(w[:-1].abs(), min=1.0))[j]
+    return pred, bound
+
+
 def read_screen_counts(counts, capacity):
     """Read the four count words once (a CUDA tensor: this is the host synchronisation the async calls leave to the
     caller; a CPU tensor works the same).  Raises EsError, naming the failure of the synchronous call's
@@ -532,6 +574,107 @@ class ShootProblem:
         """d omega / dk of every entry of a root table (the forms label_roots takes): -D_k / D_w, a CUDA tensor."""
         t = roots[0] if isinstance(roots, tuple) else roots
         return self.root_slopes(t["k"], t["w"], count=count).group_velocity
+
+    # ---- Newton tracing (C ABI section 13) ---------------------------------------------------------------------------
+    def newton(self, k, w0, max_iter=8, step_cap=None, max_shift=None, tol_percent=None, count=None):
+        """es_shoot_newton from the guesses w0 at fixed k (broadcast against w0; tensors are taken as they are): dict of CUDA
+        tensors w, resid (percent), iters, flag (int32), dwdk (-D_k / D_w at the final w) and status (uint8, that of
+        eval_points at the final pair).  step_cap caps the length of a step, max_shift the distance |w - w0| an accepted
+        root may have travelled (both default to no limit); tol_percent defaults to the 1e-3 of find_roots.  flag = 1: the
+        iteration met no leaky or singular point, the final point is PT_OK, resid < tol_percent and |w - w0| <= max_shift.
+        count as in mode_signature.  Nothing is read back."""
+        import torch
+        dmax = np.finfo(np.float64).max
+        g = self._dev(w0).reshape(-1)
+        dk = torch.broadcast_to(self._dev(k).reshape(-1), g.shape).contiguous()
+        n, dev = g.numel(), g.device
+        if count is not None:
+            assert count.is_cuda and count.numel() >= 1 and count.dtype == torch.int32
+        w, resid, dwdk = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
+        iters, flag = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        st = torch.empty(n, dtype=torch.uint8, device=dev)
+        rc = self.ctx.lib.es_shoot_newton(self.ctx.handle, self.handle, _lib.ptr(dk), _lib.ptr(g), n,
+                                          _lib.ptr(count) if count is not None else None, int(max_iter),
+                                          dmax if step_cap is None else min(float(step_cap), dmax),
+                                          dmax if max_shift is None else min(float(max_shift), dmax),
+                                          1e-3 if tol_percent is None else float(tol_percent), _lib.ptr(w), _lib.ptr(resid),
+                                          _lib.ptr(dwdk), _lib.ptr(iters), _lib.ptr(flag), _lib.ptr(st))
+        _lib.check(self.ctx.handle, rc)
+        return dict(w=w, resid=resid, iters=iters, flag=flag, dwdk=dwdk, status=st)
+
+    def _newton_from_prediction(self, kf, pred, bound, newton_kw):
+        """newton from the Hermite prediction; without a max_shift of the caller's the flag is cleared, on the device, where
+        |w - predicted| exceeds the bound of the point's coarse interval."""
+        import torch
+        given = newton_kw.get("max_shift") is not None
+        out = self.newton(kf, pred, **newton_kw)
+        if given:
+            out["max_shift"] = torch.full_like(kf, float(newton_kw["max_shift"]))
+        else:
+            out["flag"] = torch.where((out["w"] - pred).abs() <= bound, out["flag"], torch.zeros_like(out["flag"]))
+            out["max_shift"] = bound
+        out["k"] = kf
+        out["predicted"] = pred
+        return out
+
+    def densify(self, k, w, k_fine, cg=None, shift_factor=4.0, **newton_kw):
+        """One branch traced to the wavenumbers k_fine from a coarse scan: k strictly increasing with the roots w on it, as
+        SlabComplexFlow.densify does for complex roots.  (1) root_slopes at the coarse roots unless their group speed cg is
+        given, (2) the piecewise-cubic Hermite prediction at k_fine (hermite_guess), formed on the device, (3) one newton
+        call over all fine points.  Dict of CUDA tensors k, w, dwdk, resid, iters, flag, status, predicted and max_shift.
+        max_shift: a number from the caller goes to newton as it is; left out, every fine point gets the bound of its coarse
+        interval (hermite_guess, shift_factor), newton runs without a limit and the flag is cleared where |w - predicted|
+        exceeds the bound.  Nothing is read back."""
+        import torch
+        with torch.cuda.stream(self.ctx.torch_stream):
+            dk, dw, kf = (self._dev(a).reshape(-1) for a in (k, w, k_fine))
+            if dk.numel() < 2 or dw.numel() != dk.numel():
+                raise ValueError("densify needs at least two coarse rows, one root on each")
+            s = self.root_slopes(dk, dw).group_velocity if cg is None else self._dev(cg).reshape(-1)
+            pred, bound = hermite_guess(dk, dw, s, kf, shift_factor)
+            return self._newton_from_prediction(kf, pred, bound, newton_kw)
+
+    def trace_branches(self, curves, k_fine, check_signature=True, shift_factor=4.0, **newton_kw):
+        """Every branch of a coarse scan traced to the wavenumbers k_fine in ONE Newton launch.  curves: the
+        {label: (omegas, ks, cg)} of postprocess.curves_with_slopes (host arrays); k_fine: a host array.  For every label
+        whose ks are at least two and strictly increasing, the points of k_fine inside [ks[0], ks[-1]] are predicted by the
+        branch's Hermite cubic (hermite_guess_in) and handed to newton, all branches in one call, with densify's rule for
+        max_shift.  check_signature: one mode_signature call over the traced roots, and the flag is cleared, on the device,
+        where (nodes_value, nodes_flux) is not the label of the branch -- a step onto a neighbouring branch.
+        Returns TracedBranches(branches, skipped): branches[label] is a dict of views (k, w, dwdk, resid, iters, flag,
+        status, predicted, max_shift) into the tensors of the one launch, in the order of the selected k_fine; skipped lists
+        the labels with a single row or with repeated ks (two roots of a row sharing a label are never guessed at).
+        The host arrays go to the device in one copy from pinned memory that is not waited for; nothing is read back."""
+        import torch
+        kfh = np.asarray(_host_array(k_fine), dtype=np.float64).reshape(-1)
+        spans, skipped, kc, wc, sc, kf, jj, lv, lf = {}, [], [], [], [], [], [], [], []
+        n_coarse = n_fine = 0
+        for label, (om, ks, cg) in curves.items():
+            om, ks, cg = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (om, ks, cg))
+            if len(ks) < 2 or not np.all(np.diff(ks) > 0):
+                skipped.append(label)
+                continue
+            sel = kfh[(kfh >= ks[0]) & (kfh <= ks[-1])]
+            kc.append(ks); wc.append(om); sc.append(cg); kf.append(sel)
+            jj.append(n_coarse + np.clip(np.searchsorted(ks, sel, side="right") - 1, 0, len(ks) - 2))
+            lv.append(np.full(len(sel), label[0])); lf.append(np.full(len(sel), label[1]))
+            spans[label] = (n_fine, n_fine + len(sel))
+            n_coarse += len(ks)
+            n_fine += len(sel)
+        if not spans:
+            return TracedBranches({}, skipped)
+        host = np.concatenate([np.concatenate(a).astype(np.float64) for a in (kc, wc, sc, kf, jj, lv, lf)])
+        with torch.cuda.stream(self.ctx.torch_stream):
+            d = torch.from_numpy(host).pin_memory().to(f"cuda:{self.ctx.device}", non_blocking=True)
+            dkc, dwc, dsc, dkf, dj, dlv, dlf = torch.split(d, [n_coarse] * 3 + [n_fine] * 4)
+            dkf = dkf.contiguous()
+            pred, bound = hermite_guess_in(dkc, dwc, dsc, dj.to(torch.int64), dkf, shift_factor)
+            out = self._newton_from_prediction(dkf, pred.contiguous(), bound, newton_kw)
+            if check_signature:
+                sig = self.mode_signature(dkf, out["w"])
+                same = (sig.nodes_value == dlv.to(torch.int32)) & (sig.nodes_flux == dlf.to(torch.int32))
+                out["flag"] = torch.where(same, out["flag"], torch.zeros_like(out["flag"]))
+        return TracedBranches({label: {key: v[a:b] for key, v in out.items()} for label, (a, b) in spans.items()}, skipped)
 
     def _require_positive_cylinder(self):
         if not isinstance(self.eq, eqm._CylinderBase):

@@ -937,6 +937,46 @@ int es_complex_newton(es_context* ctx, const es_problem* prob, int variant,
                       double* d_w_re, double* d_w_im, double* d_resid,
                       double* d_dwdk /* [n][2], may be NULL */, int32_t* d_iters, int32_t* d_flag);
 
+/* ======================================================================================================
+ * (13) Newton tracing of real roots: the shooting determinant of section 2, all four families.  Section 11 delivers D, D_w and
+ *     D_k at a pair; this call iterates with them.  A coarse scan gives every branch with its label (section 10) and its
+ *     group speed (section 11); a piecewise-cubic Hermite prediction through those roots is then within ~1e-3 of the curve
+ *     at any k in between, and Newton with the exact D_w reaches the root in 3 - 5 steps -- a dispersion curve on thousands
+ *     of wavenumbers without marching and bracketing a (k, omega) grid of that many rows.
+ *
+ *     es_shoot_newton: one guess per lane, Newton's iteration in omega at fixed k:
+ *         w = guess; iters = 0; ok = true
+ *         repeat max_iter times:
+ *             outer, inner with d/dw at (k, w), exterior status       (the march of section 11 in (value, d/d omega) jets)
+ *             D = outer - inner, D_w likewise
+ *             if status != ES_PT_OK or D, D_w not finite or D_w == 0:  ok = false; stop
+ *             s = -D / D_w;  if |s| > step_cap: s = copysign(step_cap, s)
+ *             w += s; iters += 1
+ *             if |s| <= 1e-14 max(1, |w|): stop
+ *         at the final w (the jets of section 11, and the continuum looked at):
+ *             scale = |outer| (problems with accept_norm) or max(|outer|, |inner|)        -- the rel of section 2
+ *             resid = 100 |D| / scale,  dwdk = -D_k / D_w,  status
+ *         flag = ok && status == ES_PT_OK && resid < tol_percent && |w - guess| <= max_shift
+ *       d_w, d_resid, d_iters, d_flag [n]; d_dwdk [n] and d_status [n] may be NULL.  w is reported whatever the flag.
+ *       d_status is the status es_shoot_eval_points gives the final pair, ES_PT_CONTINUUM included (bands where the problem
+ *       has them, sign tracking otherwise, selected as in section 2); resid and dwdk are NaN where it is ES_PT_LEAKY or
+ *       ES_PT_NONFINITE.  max_iter == 0 is the final evaluation alone: w = guess with its resid and slope, resid formed
+ *       from the outer and inner es_shoot_root_slopes returns for the pair.  Pass DBL_MAX for no step_cap / max_shift.
+ *       Beside a pole of the exterior term (DESIGN.md sections 8f, 9) the iteration steps away from the pole: for
+ *       f = c / (x - p) the Newton step is x - p.  Where two roots of a row merge D_w = 0: dwdk is then not finite and the
+ *       iteration stops with ok = false if it lands there exactly.
+ *     The lanes do not depend on each other: a leaky or non-finite guess changes nothing beside it.
+ *     d_count (may be NULL): as in sections 10 - 12 -- the kernel uses min(max(*d_count, 0), n) and leaves entries beyond it
+ *     alone.  Asynchronous on the context's stream, no host read-back.  n == 0 succeeds and touches nothing (the arrays may
+ *     then be NULL).  ES_ERR_INVALID_ARG: n < 0, max_iter < 0, step_cap, max_shift or tol_percent not positive, a null
+ *     problem, any array but d_count, d_dwdk and d_status null with n > 0; ES_ERR_UNSUPPORTED: an unknown family.  Not
+ *     offered: the closed-form uniform cylinder (section 4), second derivatives, continuation in a parameter other than k.
+ * ====================================================================================================== */
+int es_shoot_newton(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_guess, int n,
+                    const int32_t* d_count /* may be NULL */, int max_iter, double step_cap, double max_shift,
+                    double tol_percent, double* d_w, double* d_resid, double* d_dwdk /* may be NULL */,
+                    int32_t* d_iters, int32_t* d_flag, uint8_t* d_status /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
