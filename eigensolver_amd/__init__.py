@@ -8,3 +8,4 @@ from .solvers import (CylinderNonUniformDensity, CylinderNonUniformFlow, Cylinde
 from .cyl_uniform import CylinderUniform  # noqa: F401
 from . import postprocess  # noqa: F401
 from .complex_flow import SlabComplexFlow, SlabFlowKH  # noqa: F401
+from .cyl_complex import CylinderComplex  # noqa: F401

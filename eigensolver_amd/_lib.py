@@ -323,4 +323,10 @@ def _sig(lib):
     # (13) Newton tracing of real roots
     if hasattr(lib, "es_shoot_newton"):                     # absent from an earlier build loaded for an A/B (tools/, --lib)
         lib.es_shoot_newton.argtypes = [vp, vp, vp, vp, i, vp, i, d, d, d, vp, vp, vp, vp, vp, vp]
+    # (14) complex frequencies on the untwisted cylinder
+    if hasattr(lib, "es_cyl_complex_eval_grid"):            # likewise
+        lib.es_cyl_complex_eval_grid.argtypes = [vp, vp, vp, i, vp, i, vp, i, i, vp, vp, vp, vp]
+        lib.es_cyl_complex_eval_points.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp]
+        lib.es_cyl_complex_find_roots.argtypes = [vp, vp, vp, i, vp, i, vp, i, i, vp, vp, vp, i, d,
+                                                  C.POINTER(ComplexRootTable), C.POINTER(i)]
     return lib

@@ -1,0 +1,197 @@
+// fp64 modified Bessel functions of integer order at COMPLEX argument, for the exterior solution of the cylinder at complex
+// frequency (es_cyl_complex.hip; include/eigensolver_amd.h section 14):  P_e(r) = a I_m(mu |r|) + b K_m(mu |r|) with
+// mu = principal sqrt(m_e).  The caller guarantees Re m_e >= 0, so mu lies in the sector |arg z| <= pi/4: only that sector
+// is supported (the continued fraction and the backward recurrence below need Re z > 0).
+//
+// Exponentially scaled forms, as in es_bessel.hpp:  Ke_n(z) = e^z K_n(z),  Ie_n(z) = e^-z I_n(z)  (the complex exponent: scipy's
+// ive scales by e^-|Re z| instead).
+//   * K_0, K_1:  |z| <= 2  the ascending series of esb::ke01 with the complex logarithm;
+//                |z| >  2  Steed's continued fraction CF2 (Temme) at order 0 -- the Chebyshev series of the real routine does
+//                          not continue off the real axis; its two coefficient sequences are real and come from the tables
+//                          of es_bessel.hpp (qdiv_int, qdiv_cf2a);
+//                then the upward recurrence K_{n+1} = K_{n-1} + (2n/z) K_n (K dominant for Re z > 0: stable).
+//   * I_n, I_{n+1}: Miller's backward recurrence for the ratio and the Wronskian I_n K_{n+1} + I_{n+1} K_n = 1/z for the
+//                normalisation (esb::ie_pair_from_k); |z| < 0.5: the ascending series.
+// Accuracy, host build against scipy.special.kve / ive (AMOS) on orders 0 ... 11, |z| in [1e-3, 300], arg z in
+// {-pi/4, 0, pi/8, pi/4} with points packed around |z| = 2 and |z| = 0.5 (tests/test_hostmath_complex.py), worst relative
+// error |f - f_ref| / |f_ref|:
+//   e^z K_n, K_{n+1}    4.9e-15, at z = 1.98: just under |z| = 2 the series of K_0 subtracts terms 12 times the result
+//   e^-z I_n, I_{n+1}   1.9e-14, at order 9, |z| = 0.004: the reference's own error -- against mpmath at 40 digits
+//                       this header is within 3e-16 there (and at every point looked at), scipy 1.9e-14; |z| >= 0.5: 9.3e-15
+// scipy is itself a few ulp off, so these are upper estimates.  The test holds the host build to twice these figures.
+#pragma once
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
+#include <type_traits>
+#include "es_bessel.hpp"
+
+#if defined(__HIPCC__)
+#define ES_HDM __host__ __device__
+#else
+#define ES_HDM
+#endif
+
+namespace esb {
+
+// ---- the complex scalar: every operator the formula text of es_shoot_device.hpp asks of its scalar type ---------------------
+struct cz {
+  double re, im;
+  cz() = default;
+  ES_HDM explicit cz(double a) : re(a), im(0.0) {}
+  ES_HDM cz(double a, double b) : re(a), im(b) {}
+};
+template <class T> struct is_cz { static constexpr bool value = false; };
+template <> struct is_cz<cz> { static constexpr bool value = true; };
+
+ES_HD cz operator-(cz a) { return cz(-a.re, -a.im); }
+ES_HD cz operator+(cz a, cz b) { return cz(a.re + b.re, a.im + b.im); }
+ES_HD cz operator-(cz a, cz b) { return cz(a.re - b.re, a.im - b.im); }
+ES_HD cz operator+(cz a, double b) { return cz(a.re + b, a.im); }
+ES_HD cz operator+(double a, cz b) { return cz(a + b.re, b.im); }
+ES_HD cz operator-(cz a, double b) { return cz(a.re - b, a.im); }
+ES_HD cz operator-(double a, cz b) { return cz(a - b.re, -b.im); }
+ES_HD cz operator*(cz a, cz b) { return cz(a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re); }
+ES_HD cz operator*(cz a, double b) { return cz(a.re * b, a.im * b); }
+ES_HD cz operator*(double a, cz b) { return cz(a * b.re, a * b.im); }
+ES_HD cz& operator*=(cz& a, double b) { a = a * b; return a; }
+ES_HD cz operator/(cz a, double b) { return cz(a.re / b, a.im / b); }
+ES_HD cz operator/(cz a, cz b) {
+  const double n = b.re * b.re + b.im * b.im;
+  return cz((a.re * b.re + a.im * b.im) / n, (a.im * b.re - a.re * b.im) / n);
+}
+ES_HD cz operator/(double a, cz b) {
+  const double n = b.re * b.re + b.im * b.im;
+  return cz((a * b.re) / n, -(a * b.im) / n);
+}
+// a b + c_ with at least one complex operand: a product and a sum (no fused form of the complex product exists)
+template <class A, class B, class C, class = typename std::enable_if<is_cz<A>::value || is_cz<B>::value || is_cz<C>::value>::type>
+ES_HD cz fma(A a, B b, C c_) { return a * b + c_; }
+ES_HD double val(cz a) { return a.re; }
+ES_HD double cz_abs2(cz a) { return a.re * a.re + a.im * a.im; }
+ES_HD double cz_abs(cz a) { return hypot(a.re, a.im); }
+ES_HD bool cz_finite(cz a) { return isfinite(a.re) && isfinite(a.im); }
+// principal square root (Re >= 0)
+ES_HD cz cz_sqrt(cz z) {
+  const double r = hypot(z.re, z.im);
+  if (r == 0.0) return cz(0.0, 0.0);
+  const double a = sqrt(0.5 * (r + fabs(z.re)));
+  const double b = 0.5 * z.im / a;
+  if (z.re >= 0.0) return cz(a, b);
+  return cz(fabs(b), copysign(a, z.im));
+}
+ES_HD cz cz_exp(cz z) {
+  const double e = exp(z.re);
+  return cz(e * cos(z.im), e * sin(z.im));
+}
+// principal logarithm
+ES_HD cz cz_log(cz z) { return cz(log(hypot(z.re, z.im)), atan2(z.im, z.re)); }
+
+// scaled K_0, K_1 (e^z K), |arg z| <= pi/4
+ES_HD void cke01(cz z, cz& k0, cz& k1) {
+  if (cz_abs2(z) <= 4.0) {
+    // esb::ke01's series, term for term, in t = z^2 / 4
+    const cz t = 0.25 * (z * z);
+    const cz lg = cz_log(0.5 * z) + kEulerGamma;
+    cz term0(1.0), i0(1.0), s0(0.0);
+    cz term1(1.0), i1(1.0), s1(1.0);
+    double hk = 0.0;
+    for (int k = 1; k < 40; ++k) {
+      const double rk = qdiv_int(1.0, k), rk1 = qdiv_int(1.0, k + 1);
+      term0 = term0 * t * (rk * rk);
+      hk += rk;
+      i0 = i0 + term0;
+      s0 = s0 + hk * term0;
+      term1 = term1 * t * (rk * rk1);
+      i1 = i1 + term1;
+      s1 = s1 + (hk + hk + rk1) * term1;
+      if (cz_abs2(term0) < 1e-36 * cz_abs2(i0)) break;
+    }
+    const cz ex = cz_exp(z);
+    k0 = ex * (s0 - lg * i0);
+    k1 = ex * (1.0 / z + lg * (0.5 * z) * i1 - 0.25 * (z * s1));
+  } else {
+    // CF2 at order 0 (Temme's sums beside Steed's continued fraction): a_i, c_i real, everything that carries z complex
+    cz b = 2.0 * (1.0 + z), d = 1.0 / b, h = d, delh = d;
+    cz q1(0.0), q2(1.0);
+    const double a1 = 0.25;
+    double c = a1, a = -a1;
+    cz q(a1);
+    cz s = 1.0 + q * delh;
+    for (int i = 2; i < 500; ++i) {
+      a -= 2.0 * (double)(i - 1);
+      c = qdiv_int(-a * c, i);
+      const cz qnew = (q1 - b * q2) * qdiv_cf2a(1.0, i, a);
+      q1 = q2;
+      q2 = qnew;
+      q = q + c * qnew;
+      b = b + 2.0;
+      d = 1.0 / (b + a * d);
+      delh = (b * d - 1.0) * delh;
+      h = h + delh;
+      const cz dels = q * delh;
+      s = s + dels;
+      if (!(cz_abs2(dels) >= 1e-34 * cz_abs2(s))) break;     // converged, or not a number
+    }
+    h = a1 * h;
+    k0 = cz_sqrt((0.5 * kPi) / z) / s;
+    k1 = (k0 * (z + 0.5 - h)) / z;
+  }
+}
+
+// scaled K_n, K_{n+1} for integer n >= 0
+ES_HD void cke_pair(int n, cz z, cz& kn, cz& knp1) {
+  cz a, b;
+  cke01(z, a, b);
+  const cz toz = 2.0 / z;
+  for (int j = 1; j <= n; ++j) {      // (a, b) = (K_{j-1}, K_j) -> (K_j, K_{j+1})
+    const cz c = a + ((double)j * toz) * b;
+    a = b;
+    b = c;
+  }
+  kn = a;
+  knp1 = b;
+}
+
+// scaled I_n, I_{n+1} by the ascending series (small |z|: all terms of one phase, no cancellation)
+ES_HD void cie_pair(int n, cz z, cz& in_, cz& inp1) {
+  const cz t = 0.25 * (z * z);
+  const cz hz = 0.5 * z;
+  cz pre(1.0);
+  for (int j = 1; j <= n; ++j) pre = pre * (hz / (double)j);
+  cz term_a(1.0), sum_a(1.0), term_b(1.0), sum_b(1.0);
+  for (int k = 1; k < 400; ++k) {
+    const double kk = (double)k;
+    term_a = (term_a * t) / (kk * (kk + (double)n));
+    term_b = (term_b * t) / (kk * (kk + (double)n + 1.0));
+    sum_a = sum_a + term_a;
+    sum_b = sum_b + term_b;
+    if (!(cz_abs2(term_a) >= 1e-36 * cz_abs2(sum_a))) break;
+  }
+  const cz ex = cz_exp(-z);
+  in_ = ex * pre * sum_a;
+  inp1 = ex * pre * (hz / ((double)n + 1.0)) * sum_b;
+}
+
+// scaled I_n, I_{n+1} from the scaled K_n, K_{n+1} at the same argument: Miller's backward recurrence for the ratio
+// I_{n+1} / I_n (I is the minimal solution for Re z > 0), the Wronskian for the normalisation.  The start index follows
+// esb::ie_pair_from_k with |z| for x; |z| is capped there so that an argument the caller never meant (an iterate that ran
+// away) costs a bounded number of steps.
+ES_HD void cie_pair_from_k(int n, cz z, cz kn, cz knp1, cz& in_, cz& inp1) {
+  const double az = cz_abs(z);
+  if (az < 0.5) { cie_pair(n, z, in_, inp1); return; }
+  const int M = n + 10 + (int)sqrt(40.0 * fmin(az, 1.0e6));
+  const cz toz = 2.0 / z;
+  cz ip(0.0), ic(1.0);                                        // I_{M+1}, I_M up to a common factor, kept within range
+  for (int k = M; k > n; --k) {                               // (ip, ic) = (I_{k+1}, I_k) -> (I_k, I_{k-1})
+    const cz im = ((double)k * toz) * ic + ip;
+    ip = ic;
+    ic = im;
+    if (cz_abs2(ic) > 1e200) { ic = 1e-100 * ic; ip = 1e-100 * ip; }
+  }
+  const cz f = ip / ic;                                       // I_{n+1} / I_n
+  in_ = 1.0 / (z * (f * kn + knp1));
+  inp1 = f * in_;
+}
+
+}  // namespace esb

@@ -3,8 +3,10 @@
 // See include/eigensolver_amd.h section (6) for the reference lines this replaces and oracle/slab_complex.py for the
 // CPU restatement.  The formulas (coefficients, exterior, adjoint march, boundary) are the W = 1 instances of
 // es_complex_shared.hpp, the text es_complex_slopes.hip differentiates; here are the kernels around them: one (k, omega)
-// point per lane, the forward march of the eigenfunction, the winding-number flags and the secant refinement.
-#include "es_complex_shared.hpp"
+// point per lane, the forward march of the eigenfunction, the winding-number flags and the secant refinement.  The search is
+// shared with the cylinder (es_cyl_complex.hip) through es_complex_roots.hpp: the flag and emit kernels live here behind
+// cx_candidates, the refinement loop and the host side of a find_roots call are the header's.
+#include "es_complex_roots.hpp"
 
 namespace {
 using namespace es_complex_shared;
@@ -16,10 +18,6 @@ __device__ __forceinline__ void cx_shoot_point(const ShootDev& P, int variant, d
   const CxMatch<1> B = cx_eval<1>(P, variant, k, w, sb);
   D = (B.st == ES_PT_OK) ? B.outer.c[0] - B.inner.c[0] : cx{NAN, NAN};
   rel = B.rel; st = B.st;
-}
-
-__device__ __forceinline__ cx cx_pick_w(int w_mode, double k, double wre, double wim) {
-  return (w_mode == ES_W_PHASE_SPEED) ? cx{k * wre, k * wim} : cx{wre, wim};
 }
 
 // grid (n_re > 0: index -> (row, i_im, i_re)) or point list (n_re == 0)
@@ -215,42 +213,40 @@ __global__ __launch_bounds__(256) void cx_emit_kernel(const double* __restrict__
   half_im[pos] = 0.5 * (b.im - a.im);
 }
 
-// complex secant iteration, one candidate per lane; uniform trip count (all lanes evaluate together)
+// complex secant iteration (cx_refine_candidate), one candidate per lane
 __global__ __launch_bounds__(64) void cx_refine_kernel(ShootDev P, int variant, es_complex_root_table tab,
                                                        const double* __restrict__ half_re,
                                                        const double* __restrict__ half_im, int n, int n_iter,
                                                        double tol_percent) {
   __shared__ double sb[CX_LDS_DOUBLES];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool in = i < n;
-  const double k = in ? tab.d_k[i] : 1.0;
-  const cx centre = in ? cx{tab.d_w_re[i], tab.d_w_im[i]} : cx{1.0, 0.1};
-  const cx half = in ? cx{half_re[i], half_im[i]} : cx{0.1, 0.1};
-  cx w0 = centre, w1 = centre + cx{0.5 * half.re, 0.5 * half.im};
-  cx f0, f1; double rel0, rel1; uint8_t s0, s1;
-  cx_shoot_point(P, variant, k, w0, f0, rel0, s0, sb);
-  cx_shoot_point(P, variant, k, w1, f1, rel1, s1, sb);
-  for (int it = 0; it < n_iter; ++it) {
-    const cx df = f1 - f0;
-    cx w2 = w1 - f1 * ((w1 - w0) / df);
-    if (!cfinite(w2) || cabs2(df) == 0.0) w2 = w1;          // converged (f1 == f0) or broken: stay
-    w0 = w1; f0 = f1;
-    w1 = w2;
-    cx_shoot_point(P, variant, k, w1, f1, rel1, s1, sb);
-    if (!cfinite(f1)) { w1 = w0; f1 = f0; }                 // stepped onto a leaky / singular point: back off
-  }
-  // rel of the final iterate
-  cx_shoot_point(P, variant, k, w1, f1, rel1, s1, sb);
-  if (in) {
-    const double dist2 = cabs2(w1 - centre), diag2 = 4.0 * cabs2(half);
-    tab.d_w_re[i] = w1.re;
-    tab.d_w_im[i] = w1.im;
-    tab.d_resid[i] = rel1;
-    tab.d_flag[i] = (s1 == ES_PT_OK && rel1 < tol_percent && dist2 <= 4.0 * diag2) ? 1 : 0;
-  }
+  cx_refine_candidate([&](double k, cx w, cx& f, double& rel, uint8_t& st) { cx_shoot_point(P, variant, k, w, f, rel, st, sb); },
+                      tab, half_re, half_im, i, n, n_iter, tol_percent);
 }
 
 }  // namespace
+
+int es_complex_shared::cx_candidates(es_context* ctx, const double* d_k, const double* d_w_re, int n_re, const double* d_w_im,
+                                     int n_im, int w_mode, long cells, const double* d_D_re, const double* d_D_im,
+                                     const uint8_t* d_status, const es_complex_root_table& table, int* total) {
+  int rc = es_ensure_scan_scratch(ctx, (size_t)cells);
+  if (rc) return rc;
+  const int nblocks = (int)((cells + 255) / 256);
+  hipLaunchKernelGGL(cx_flag_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_D_re, d_D_im, d_status, n_re, n_im,
+                     cells, ctx->d_masks, ctx->d_block_counts);
+  ES_HIP_CHECK(ctx, hipGetLastError());
+  rc = es_scan_block_counts(ctx, nblocks, total);
+  if (rc) return rc;
+  const int n = *total < table.capacity ? *total : table.capacity;
+  if (n > 0) {
+    rc = es_ensure_scratch(ctx, 2 * (size_t)n * sizeof(double));
+    if (rc) return rc;
+    double* half = (double*)ctx->d_scratch;
+    hipLaunchKernelGGL(cx_emit_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_k, d_w_re, d_w_im, n_re, n_im,
+                       w_mode, cells, ctx->d_masks, ctx->d_block_counts, table, half, half + n);
+  }
+  return ES_SUCCESS;
+}
 
 extern "C" int es_complex_eval_grid(es_context* ctx, const es_problem* prob, int variant, const double* d_k, int nk,
                                     const double* d_w_re, int n_re, const double* d_w_im, int n_im, int w_mode,
@@ -293,39 +289,11 @@ extern "C" int es_complex_find_roots(es_context* ctx, const es_problem* prob, in
   if (!ctx) return ES_ERR_INVALID_ARG;
   int rc = check_cx(ctx, prob, variant);
   if (rc) return rc;
-  ES_REQUIRE(ctx, table && out_count, "null pointer");
-  ES_REQUIRE(ctx, nk >= 0 && n_re >= 0 && n_im >= 0 && n_iter >= 0 && n_iter <= 1000 && table->capacity >= 0, "size");
-  ES_REQUIRE(ctx, w_mode == ES_W_ABSOLUTE || w_mode == ES_W_PHASE_SPEED, "w_mode");
-  *out_count = 0;
-  const long cells = (long)nk * n_re * n_im;
-  if (cells == 0) return ES_SUCCESS;
-  ES_REQUIRE(ctx, d_k && d_w_re && d_w_im && d_D_re && d_D_im && d_status, "null pointer");
-  ES_REQUIRE(ctx, table->capacity == 0 || (table->d_k && table->d_w_re && table->d_w_im && table->d_resid &&
-                                           table->d_row && table->d_flag), "null root table arrays");
-  ES_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  rc = es_ensure_scan_scratch(ctx, (size_t)cells);
-  if (rc) return rc;
-  const int nblocks = (int)((cells + 255) / 256);
-  hipLaunchKernelGGL(cx_flag_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_D_re, d_D_im, d_status, n_re, n_im,
-                     cells, ctx->d_masks, ctx->d_block_counts);
-  ES_HIP_CHECK(ctx, hipGetLastError());
-  int total = 0;
-  rc = es_scan_block_counts(ctx, nblocks, &total);
-  if (rc) return rc;
-  *out_count = total;
-  const int n = total < table->capacity ? total : table->capacity;
-  if (n > 0) {
-    rc = es_ensure_scratch(ctx, 2 * (size_t)n * sizeof(double));
-    if (rc) return rc;
-    double* half = (double*)ctx->d_scratch;
-    hipLaunchKernelGGL(cx_emit_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, d_k, d_w_re, d_w_im, n_re, n_im,
-                       w_mode, cells, ctx->d_masks, ctx->d_block_counts, *table, half, half + n);
-    hipLaunchKernelGGL(cx_refine_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, prob->dev, variant, *table,
-                       half, half + n, n, n_iter, tol_percent);
-    ES_HIP_CHECK(ctx, hipGetLastError());
-    ES_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return (total > table->capacity) ? ES_ERR_CAPACITY : ES_SUCCESS;
+  return cx_find_roots_host(ctx, d_k, nk, d_w_re, n_re, d_w_im, n_im, w_mode, d_D_re, d_D_im, d_status, n_iter, table, out_count,
+                            [&](const es_complex_root_table& tab, const double* half_re, const double* half_im, int n) {
+                              hipLaunchKernelGGL(cx_refine_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, prob->dev,
+                                                 variant, tab, half_re, half_im, n, n_iter, tol_percent);
+                            });
 }
 
 extern "C" int es_complex_eigenfunction(es_context* ctx, const es_problem* prob, int variant, const double* d_k,

@@ -977,6 +977,44 @@ int es_shoot_newton(es_context* ctx, const es_problem* prob, const double* d_k, 
                     double tol_percent, double* d_w, double* d_resid, double* d_dwdk /* may be NULL */,
                     int32_t* d_iters, int32_t* d_flag, uint8_t* d_status /* may be NULL */);
 
+/* ======================================================================================================
+ * (14) Complex frequencies on the untwisted cylinder: the determinant of section 2 at omega = omega_r + i omega_i and its
+ *     root search -- the unstable (Kelvin-Helmholtz) modes of a cylinder whose axial jet is fast enough, where the root leaves
+ *     the real axis and sections 2 and 13 find nothing.  ES_GEOM_CYLINDER problems only (non-uniform density or axial flow,
+ *     any m, both axis conditions, both signs of r); every other geometry gets ES_ERR_UNSUPPORTED (the flow slab has
+ *     section 6, whose calls in turn keep refusing cylinders).  Values only.
+ *     What is computed: the interior of section 2 -- the same node grid, the same coefficient formulas, one classical RK4
+ *     step per interval, the adjoint row march, the axis condition by superposition -- in complex arithmetic, and the
+ *     exterior P_e = a I_m(mu |r|) + b K_m(mu |r|) with mu = principal sqrt(m_e), K and I at complex argument, the
+ *     reference's far-field initial values.  The exterior solution is normalised by its own complex boundary value,
+ *     P_e(boundary) = 1 (section 2 divides by |P_e| and keeps a sign), so at omega_i = 0
+ *         D_c = sign(P_e(boundary)) D of es_shoot_eval_points,    Im D_c = 0.
+ *     outer = xi_e, inner = xi_i, D_c = outer - inner, rel = 100 |D_c| / max(|outer|, |inner|) (|outer| alone for problems
+ *     with accept_norm).  D_c(k, conj omega) = conj D_c(k, omega).
+ *     Status: ES_PT_LEAKY where Re(m_e) < 0 (the rule of section 6, and of section 2 on the real axis; it keeps mu in the
+ *     sector |arg mu| <= pi/4); ES_PT_NONFINITE where m_e, xi_e_const or the result is not finite.  ES_PT_CONTINUUM is never
+ *     reported: off the real axis the coefficients have no zero on the grid, and on it callers have section 2.  D_c, rel,
+ *     outer and inner are NaN unless the status is ES_PT_OK.
+ *     Grid layout, w_mode, the cell rule, the secant refinement, the flag, the order of the table, es_complex_root_table and
+ *     the capacity convention (ES_ERR_CAPACITY with the full count in *out_count and the first `capacity` records written)
+ *     are those of section 6; argument checks likewise, without `variant`.  A call with no points (a zero size) succeeds and
+ *     touches nothing.  The eval calls are asynchronous on the context's stream; es_cyl_complex_find_roots synchronises.
+ *     es_cyl_complex_eval_points: d_outer, d_inner (each may be NULL) receive the two sides as interleaved (re, im) pairs [n].
+ * ====================================================================================================== */
+int es_cyl_complex_eval_grid(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
+                             const double* d_w_re, int n_re, const double* d_w_im, int n_im, int w_mode,
+                             double* d_D_re, double* d_D_im, double* d_rel /* may be NULL */, uint8_t* d_status);
+
+int es_cyl_complex_eval_points(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w_re,
+                               const double* d_w_im, int n, double* d_D_re, double* d_D_im,
+                               double* d_rel /* may be NULL */, uint8_t* d_status,
+                               double* d_outer /* [n][2], may be NULL */, double* d_inner /* [n][2], may be NULL */);
+
+int es_cyl_complex_find_roots(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
+                              const double* d_w_re, int n_re, const double* d_w_im, int n_im, int w_mode,
+                              const double* d_D_re, const double* d_D_im, const uint8_t* d_status, int n_iter,
+                              double tol_percent, es_complex_root_table* table, int* out_count);
+
 #ifdef __cplusplus
 }
 #endif
