@@ -329,4 +329,8 @@ def _sig(lib):
         lib.es_cyl_complex_eval_points.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp]
         lib.es_cyl_complex_find_roots.argtypes = [vp, vp, vp, i, vp, i, vp, i, i, vp, vp, vp, i, d,
                                                   C.POINTER(ComplexRootTable), C.POINTER(i)]
+    # (15) slopes and Newton tracing of complex cylinder roots
+    if hasattr(lib, "es_cyl_complex_root_slopes"):          # likewise
+        lib.es_cyl_complex_root_slopes.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, vp, vp]
+        lib.es_cyl_complex_newton.argtypes = [vp, vp, vp, vp, vp, i, vp, i, d, d, d, vp, vp, vp, vp, vp, vp]
     return lib

@@ -80,7 +80,109 @@ def _distinct(w, tol=1e-8):
     return np.array(keep, dtype=complex)
 
 
-class SlabComplexFlow:
+class ComplexTracing:
+    """Slopes and Newton tracing of complex roots, written once for the geometries that have the two C calls (sections 12 and
+    15 of include/eigensolver_amd.h): root_slopes, group_velocity, newton and densify.  A class that mixes this in has ctx,
+    P_TOL, problem(mode, **select) and the two calls, _slopes_call(problem, *args) and _newton_call(problem, *args), args
+    being the C arguments after the problem (and, for the slab, the variant).  `select` stands for the keywords that pick the
+    problem beside the mode (_SELECT: none for the slab, m for the cylinder)."""
+    _SELECT = ()
+
+    def _pairs(self, mode, k, w, **select):
+        """(problem, k, Re w, Im w) on the device, k broadcast against the complex w; tensors are taken as they are."""
+        import torch
+        p = self.problem(mode, **select)
+        dev = f"cuda:{self.ctx.device}"
+        if isinstance(w, torch.Tensor):
+            w = w.to(device=dev, dtype=torch.complex128).reshape(-1)
+        else:
+            w = torch.as_tensor(np.asarray(w, dtype=complex).reshape(-1), device=dev)
+        dk = torch.broadcast_to(p._dev(k).reshape(-1), w.shape).contiguous()
+        return p, dk, w.real.contiguous(), w.imag.contiguous()
+
+    @staticmethod
+    def _count_ptr(count):
+        import torch
+        if count is None:
+            return None
+        assert count.is_cuda and count.numel() >= 1 and count.dtype == torch.int32
+        return _lib.ptr(count)
+
+    def root_slopes(self, mode, k, w, count=None, **select):
+        """The root-slopes call at the complex (k, omega) pairs: D_c of eval_points with its exact derivatives in omega
+        (holomorphic) and k, a tangent-linear march with no difference step -> ComplexRootSlopes.  k is broadcast against
+        w; both may be tensors.  count: an int32 CUDA tensor holding the number of valid pairs; entries past
+        min(count, n) are left as allocated.  Nothing is read back."""
+        import torch
+        p, dk, dre, dim = self._pairs(mode, k, w, **select)
+        n, dev = dk.numel(), dk.device
+        outer = torch.empty((3, n), dtype=torch.complex128, device=dev)
+        inner = torch.empty((3, n), dtype=torch.complex128, device=dev)
+        st = torch.empty(n, dtype=torch.uint8, device=dev)
+        rc = self._slopes_call(p, _lib.ptr(dk), _lib.ptr(dre), _lib.ptr(dim), n, self._count_ptr(count), _lib.ptr(outer),
+                               _lib.ptr(inner), _lib.ptr(st))
+        _lib.check(self.ctx.handle, rc)
+        diff = outer - inner
+        return ComplexRootSlopes(outer, inner, diff[0], diff[1], diff[2], st)
+
+    def group_velocity(self, mode, roots, count=None, **select):
+        """d omega / dk (complex) of every entry of a find_roots table: -D_k / D_w, a CUDA tensor."""
+        t = roots[0] if isinstance(roots, tuple) else roots
+        return self.root_slopes(mode, t["k"], t["w"], count=count, **select).group_velocity
+
+    def newton(self, mode, k, w0, max_iter=8, step_cap=None, max_shift=None, tol_percent=None, count=None, **select):
+        """The Newton call from the guesses w0 at fixed k (broadcast against w0): dict of CUDA tensors w (complex128),
+        resid (percent), iters, flag (int32) and dwdk (complex128, -D_k / D_w at the final w).  step_cap caps the length
+        of a step, max_shift the distance |w - w0| an accepted root may have travelled (both default to no limit);
+        tol_percent defaults to P_TOL.  flag = 1: the iteration met no leaky or singular point, the final point is
+        ES_PT_OK, resid < tol_percent and |w - w0| <= max_shift.  Nothing is read back."""
+        import torch
+        p, dk, gre, gim = self._pairs(mode, k, w0, **select)
+        n, dev = dk.numel(), dk.device
+        wre, wim, resid = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
+        dwdk = torch.empty(n, dtype=torch.complex128, device=dev)
+        iters, flag = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        rc = self._newton_call(p, _lib.ptr(dk), _lib.ptr(gre), _lib.ptr(gim), n, self._count_ptr(count), int(max_iter),
+                               DBL_MAX if step_cap is None else min(float(step_cap), DBL_MAX),
+                               DBL_MAX if max_shift is None else min(float(max_shift), DBL_MAX),
+                               self.P_TOL if tol_percent is None else float(tol_percent), _lib.ptr(wre), _lib.ptr(wim),
+                               _lib.ptr(resid), _lib.ptr(dwdk), _lib.ptr(iters), _lib.ptr(flag))
+        _lib.check(self.ctx.handle, rc)
+        return dict(w=torch.complex(wre, wim), resid=resid, iters=iters, flag=flag, dwdk=dwdk)
+
+    def densify(self, mode, k, w, k_fine, shift_factor=4.0, **newton_kw):
+        """One branch traced to the wavenumbers k_fine from a coarse scan: k strictly increasing with the roots w on it.
+        (1) root_slopes at the coarse roots, (2) the complex piecewise-cubic Hermite prediction at k_fine (the cubic of the
+        end interval continued outside [k[0], k[-1]]), formed on the device, (3) one newton call over all fine points.
+        Dict of CUDA tensors k, w, dwdk, resid, iters, flag, predicted and max_shift.  Nothing is read back.
+        max_shift: a number from the caller goes to newton as it is.  Left out, every fine point gets the bound of its
+        coarse interval [k_j, k_j+1], shift_factor (4) times the larger of the interval's two end-point Hermite defects
+            |w_j+1 - w_j - h s_j|,  |w_j+1 - w_j - h s_j+1|      (s = d omega / dk, h = k_j+1 - k_j)
+        -- how far the tangent from one end misses the root at the other, a scale for how far the curve bends inside the
+        interval and so for how far the cubic can lie from it -- and no less than 1e-8 max(1, |w_j|); newton then runs
+        without a limit and the flag is cleared, on the device, where |w - predicted| exceeds the bound."""
+        import torch
+        select = {name: newton_kw.pop(name) for name in self._SELECT if name in newton_kw}
+        p, dk, dre, dim = self._pairs(mode, k, w, **select)
+        wc = torch.complex(dre, dim)
+        if dk.numel() < 2:
+            raise ValueError("densify needs at least two coarse rows")
+        kf = p._dev(k_fine).reshape(-1)
+        s = self.root_slopes(mode, dk, wc, **select).group_velocity
+        pred, bound = hermite_guess(dk, wc, s, kf, shift_factor)
+        given = newton_kw.get("max_shift") is not None
+        out = self.newton(mode, kf, pred, **newton_kw, **select)
+        if given:
+            out["max_shift"] = torch.full_like(kf, float(newton_kw["max_shift"]))
+        else:
+            out["flag"] = torch.where((out["w"] - pred).abs() <= bound, out["flag"], torch.zeros_like(out["flag"]))
+            out["max_shift"] = bound
+        out["k"] = kf
+        out["predicted"] = pred
+        return out
+
+
+class SlabComplexFlow(ComplexTracing):
     """Complex-frequency flow slab: D_c on (k, Re omega, Im omega) grids, roots, and the reference's worker signature."""
     P_TOL = 4.0                                     # SF-X:301
 
@@ -194,100 +296,12 @@ class SlabComplexFlow:
         x_int = torch.linspace(p.desc.x_boundary, p.desc.x_end, N, dtype=torch.float64, device=dev)
         return dict(x_int=x_int, value_int=vi, flux_int=fi, x_ext=xe, value_ext=ve, flux_ext=fe, status=st)
 
-    # ---- slopes and Newton tracing (C ABI section 12) ------------------------------------------------------------------
-    def _pairs(self, mode, k, w):
-        """(problem, k, Re w, Im w) on the device, k broadcast against the complex w; tensors are taken as they are."""
-        import torch
-        p = self.problem(mode)
-        dev = f"cuda:{self.ctx.device}"
-        if isinstance(w, torch.Tensor):
-            w = w.to(device=dev, dtype=torch.complex128).reshape(-1)
-        else:
-            w = torch.as_tensor(np.asarray(w, dtype=complex).reshape(-1), device=dev)
-        dk = torch.broadcast_to(p._dev(k).reshape(-1), w.shape).contiguous()
-        return p, dk, w.real.contiguous(), w.imag.contiguous()
+    # ---- slopes and Newton tracing (C ABI section 12): ComplexTracing over these two calls ----------------------------------
+    def _slopes_call(self, p, *args):
+        return self.ctx.lib.es_complex_root_slopes(self.ctx.handle, p.handle, self.variant, *args)
 
-    @staticmethod
-    def _count_ptr(count):
-        import torch
-        if count is None:
-            return None
-        assert count.is_cuda and count.numel() >= 1 and count.dtype == torch.int32
-        return _lib.ptr(count)
-
-    def root_slopes(self, mode, k, w, count=None):
-        """es_complex_root_slopes at the complex (k, omega) pairs: D_c of eval_points with its exact derivatives in omega
-        (holomorphic) and k, a tangent-linear march with no difference step -> ComplexRootSlopes.  k is broadcast against
-        w; both may be tensors.  count: an int32 CUDA tensor holding the number of valid pairs; entries past
-        min(count, n) are left as allocated.  Nothing is read back."""
-        import torch
-        p, dk, dre, dim = self._pairs(mode, k, w)
-        n, dev = dk.numel(), dk.device
-        outer = torch.empty((3, n), dtype=torch.complex128, device=dev)
-        inner = torch.empty((3, n), dtype=torch.complex128, device=dev)
-        st = torch.empty(n, dtype=torch.uint8, device=dev)
-        rc = self.ctx.lib.es_complex_root_slopes(self.ctx.handle, p.handle, self.variant, _lib.ptr(dk), _lib.ptr(dre),
-                                                 _lib.ptr(dim), n, self._count_ptr(count), _lib.ptr(outer),
-                                                 _lib.ptr(inner), _lib.ptr(st))
-        _lib.check(self.ctx.handle, rc)
-        diff = outer - inner
-        return ComplexRootSlopes(outer, inner, diff[0], diff[1], diff[2], st)
-
-    def group_velocity(self, mode, roots, count=None):
-        """d omega / dk (complex) of every entry of a find_roots table: -D_k / D_w, a CUDA tensor."""
-        t = roots[0] if isinstance(roots, tuple) else roots
-        return self.root_slopes(mode, t["k"], t["w"], count=count).group_velocity
-
-    def newton(self, mode, k, w0, max_iter=8, step_cap=None, max_shift=None, tol_percent=None, count=None):
-        """es_complex_newton from the guesses w0 at fixed k (broadcast against w0): dict of CUDA tensors w (complex128),
-        resid (percent), iters, flag (int32) and dwdk (complex128, -D_k / D_w at the final w).  step_cap caps the length
-        of a step, max_shift the distance |w - w0| an accepted root may have travelled (both default to no limit);
-        tol_percent defaults to P_TOL.  flag = 1: the iteration met no leaky or singular point, the final point is
-        ES_PT_OK, resid < tol_percent and |w - w0| <= max_shift.  Nothing is read back."""
-        import torch
-        p, dk, gre, gim = self._pairs(mode, k, w0)
-        n, dev = dk.numel(), dk.device
-        wre, wim, resid = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
-        dwdk = torch.empty(n, dtype=torch.complex128, device=dev)
-        iters, flag = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
-        rc = self.ctx.lib.es_complex_newton(self.ctx.handle, p.handle, self.variant, _lib.ptr(dk), _lib.ptr(gre), _lib.ptr(gim),
-                                            n, self._count_ptr(count), int(max_iter),
-                                            DBL_MAX if step_cap is None else min(float(step_cap), DBL_MAX),
-                                            DBL_MAX if max_shift is None else min(float(max_shift), DBL_MAX),
-                                            self.P_TOL if tol_percent is None else float(tol_percent), _lib.ptr(wre),
-                                            _lib.ptr(wim), _lib.ptr(resid), _lib.ptr(dwdk), _lib.ptr(iters), _lib.ptr(flag))
-        _lib.check(self.ctx.handle, rc)
-        return dict(w=torch.complex(wre, wim), resid=resid, iters=iters, flag=flag, dwdk=dwdk)
-
-    def densify(self, mode, k, w, k_fine, shift_factor=4.0, **newton_kw):
-        """One branch traced to the wavenumbers k_fine from a coarse scan: k strictly increasing with the roots w on it.
-        (1) root_slopes at the coarse roots, (2) the complex piecewise-cubic Hermite prediction at k_fine (the cubic of the
-        end interval continued outside [k[0], k[-1]]), formed on the device, (3) one newton call over all fine points.
-        Dict of CUDA tensors k, w, dwdk, resid, iters, flag, predicted and max_shift.  Nothing is read back.
-        max_shift: a number from the caller goes to newton as it is.  Left out, every fine point gets the bound of its
-        coarse interval [k_j, k_j+1], shift_factor (4) times the larger of the interval's two end-point Hermite defects
-            |w_j+1 - w_j - h s_j|,  |w_j+1 - w_j - h s_j+1|      (s = d omega / dk, h = k_j+1 - k_j)
-        -- how far the tangent from one end misses the root at the other, a scale for how far the curve bends inside the
-        interval and so for how far the cubic can lie from it -- and no less than 1e-8 max(1, |w_j|); newton then runs
-        without a limit and the flag is cleared, on the device, where |w - predicted| exceeds the bound."""
-        import torch
-        p, dk, dre, dim = self._pairs(mode, k, w)
-        wc = torch.complex(dre, dim)
-        if dk.numel() < 2:
-            raise ValueError("densify needs at least two coarse rows")
-        kf = p._dev(k_fine).reshape(-1)
-        s = self.root_slopes(mode, dk, wc).group_velocity
-        pred, bound = hermite_guess(dk, wc, s, kf, shift_factor)
-        given = newton_kw.get("max_shift") is not None
-        out = self.newton(mode, kf, pred, **newton_kw)
-        if given:
-            out["max_shift"] = torch.full_like(kf, float(newton_kw["max_shift"]))
-        else:
-            out["flag"] = torch.where((out["w"] - pred).abs() <= bound, out["flag"], torch.zeros_like(out["flag"]))
-            out["max_shift"] = bound
-        out["k"] = kf
-        out["predicted"] = pred
-        return out
+    def _newton_call(self, p, *args):
+        return self.ctx.lib.es_complex_newton(self.ctx.handle, p.handle, self.variant, *args)
 
     # ---- perturbation fields (C ABI section 9) -----------------------------------------------------------------------
     def polarisation(self, mode, k, w, n_ext=500, reference_quirks=True):

@@ -2,6 +2,8 @@
 // 6 and 14): the candidate cells (winding-number flags, ordered compaction, cell centres: the kernels live in es_complex.hip),
 // the complex secant refinement over an evaluator, and the host side of a find_roots call.  The flow slab (es_complex.hip)
 // and the cylinder (es_cyl_complex.hip) differ in the evaluator of the refinement kernel and in their argument check only.
+// Beside it the Newton rule of sections 12 and 15 (cx_newton_lane), over an evaluator in the same way: es_complex_slopes.hip
+// and es_cyl_complex_slopes.hip.
 #pragma once
 #include "es_complex_shared.hpp"
 
@@ -51,6 +53,64 @@ __device__ __forceinline__ void cx_refine_candidate(Eval eval, es_complex_root_t
     tab.d_resid[i] = rel1;
     tab.d_flag[i] = (s1 == ES_PT_OK && rel1 < tol_percent && dist2 <= 4.0 * diag2) ? 1 : 0;
   }
+}
+
+// What one evaluation hands the Newton rule: D_c with its derivatives in omega and k (Dk: the final evaluation only), rel in
+// percent and the status.
+struct CxNewtonPoint {
+  cx D, Dw, Dk;
+  double rel;
+  uint8_t st;
+};
+
+// Newton in omega at fixed k for guess i of the workgroup's cnt (es_complex_newton, es_cyl_complex_newton).  step(k, w) is
+// the evaluation with d/d omega, last(k, w) the one with d/dk as well; both have barriers, so every lane of the workgroup
+// makes this call.  A lane that has stopped keeps evaluating at its frozen omega; the workgroup leaves the loop together once
+// no lane is active.  Lanes past cnt iterate on dummy inputs and store nothing.
+template <class Step, class Final>
+__device__ __forceinline__ void cx_newton_lane(Step step, Final last, const double* __restrict__ kv,
+                                               const double* __restrict__ gre, const double* __restrict__ gim, int i, int cnt,
+                                               int max_iter, double step_cap, double max_shift, double tol_percent,
+                                               double* __restrict__ wre, double* __restrict__ wim, double* __restrict__ resid,
+                                               double* __restrict__ dwdk, int32_t* __restrict__ iters_out,
+                                               int32_t* __restrict__ flag_out) {
+  const bool in = i < cnt;
+  const double k = in ? kv[i] : 1.0;
+  const cx guess = in ? cx{gre[i], gim[i]} : cx{1.0, 0.1};
+  cx w = guess;
+  int iters = 0;
+  bool ok = true, active = in;
+  for (int it = 0; it < max_iter; ++it) {                      // max_iter is uniform: every lane reaches the vote
+    const CxNewtonPoint E = step(k, w);
+    if (active) {
+      const cx D = E.D, Dw = E.Dw;
+      if (E.st != ES_PT_OK || !cfinite(D) || !cfinite(Dw) || (Dw.re == 0.0 && Dw.im == 0.0)) {
+        ok = false;
+        active = false;
+      } else {
+        cx s = -(D / Dw);
+        const double a = cabs_(s);
+        if (a > step_cap) s = (step_cap / a) * s;
+        w = w + s;
+        ++iters;
+        if (cabs_(s) <= 1e-14 * fmax(1.0, cabs_(w))) active = false;
+      }
+    }
+    if (!__syncthreads_or(active ? 1 : 0)) break;
+  }
+  const CxNewtonPoint E = last(k, w);
+  if (!in) return;
+  const bool good = E.st == ES_PT_OK;
+  const cx slope = good ? -(E.Dk / E.Dw) : cx{NAN, NAN};
+  wre[i] = w.re;
+  wim[i] = w.im;
+  resid[i] = E.rel;
+  if (dwdk) {
+    dwdk[2 * (size_t)i] = slope.re;
+    dwdk[2 * (size_t)i + 1] = slope.im;
+  }
+  iters_out[i] = iters;
+  flag_out[i] = (ok && good && E.rel < tol_percent && cabs_(w - guess) <= max_shift) ? 1 : 0;
 }
 
 // Host side of a find_roots call after the problem was accepted.  launch_refine(table, half_re, half_im, n) enqueues the

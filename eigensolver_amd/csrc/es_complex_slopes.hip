@@ -6,7 +6,7 @@
 //
 // One (k, omega) pair per lane, 64-thread workgroups, the profile table staged chunk by chunk in LDS (cx_stage_chunk):
 // every lane of a workgroup reaches every barrier.  Lanes past the count march on dummy inputs and store nothing.
-#include "es_complex_shared.hpp"
+#include "es_complex_roots.hpp"
 
 namespace {
 using namespace es_complex_shared;
@@ -41,8 +41,8 @@ __global__ __launch_bounds__(64) void cx_slopes_kernel(ShootDev P, int variant, 
   if (status) status[i] = E.st;
 }
 
-// Newton in omega at fixed k, one guess per lane.  A lane that has stopped keeps evaluating at its frozen omega (the staging
-// barriers need all 64 lanes); the workgroup leaves the loop together once no lane is active.
+// Newton in omega at fixed k, one guess per lane: the rule of cx_newton_lane (es_complex_roots.hpp) over the slab's evaluation
+// at jet widths 2 (the steps) and 3 (the final point).
 __global__ __launch_bounds__(64) void cx_newton_kernel(ShootDev P, int variant, const double* __restrict__ kv,
                                                        const double* __restrict__ gre, const double* __restrict__ gim, int n,
                                                        const int32_t* __restrict__ d_count, int max_iter, double step_cap,
@@ -54,44 +54,16 @@ __global__ __launch_bounds__(64) void cx_newton_kernel(ShootDev P, int variant, 
   const int cnt = es_count_clamped(d_count, n);
   if ((int)(blockIdx.x * blockDim.x) >= cnt) return;           // the whole workgroup lies past the count
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool in = i < cnt;
-  const double k = in ? kv[i] : 1.0;
-  const cx guess = in ? cx{gre[i], gim[i]} : cx{1.0, 0.1};
-  cx w = guess;
-  int iters = 0;
-  bool ok = true, active = in;
-  for (int it = 0; it < max_iter; ++it) {                      // max_iter is uniform: every lane reaches the vote
-    const CxMatch<2> E = cx_eval<2>(P, variant, k, w, sb);
-    if (active) {
-      const cx D = E.outer.c[0] - E.inner.c[0], Dw = E.outer.c[1] - E.inner.c[1];
-      if (E.st != ES_PT_OK || !cfinite(D) || !cfinite(Dw) || (Dw.re == 0.0 && Dw.im == 0.0)) {
-        ok = false;
-        active = false;
-      } else {
-        cx s = -(D / Dw);
-        const double a = cabs_(s);
-        if (a > step_cap) s = (step_cap / a) * s;
-        w = w + s;
-        ++iters;
-        if (cabs_(s) <= 1e-14 * fmax(1.0, cabs_(w))) active = false;
-      }
-    }
-    if (!__syncthreads_or(active ? 1 : 0)) break;
-  }
-  const CxMatch<3> E = cx_eval<3>(P, variant, k, w, sb);
-  if (!in) return;
-  const cx Dw = E.outer.c[1] - E.inner.c[1], Dk = E.outer.c[2] - E.inner.c[2];
-  const bool good = E.st == ES_PT_OK;
-  const cx slope = good ? -(Dk / Dw) : cx{NAN, NAN};
-  wre[i] = w.re;
-  wim[i] = w.im;
-  resid[i] = E.rel;
-  if (dwdk) {
-    dwdk[2 * (size_t)i] = slope.re;
-    dwdk[2 * (size_t)i + 1] = slope.im;
-  }
-  iters_out[i] = iters;
-  flag_out[i] = (ok && good && E.rel < tol_percent && cabs_(w - guess) <= max_shift) ? 1 : 0;
+  cx_newton_lane(
+      [&](double k, cx w) {
+        const CxMatch<2> E = cx_eval<2>(P, variant, k, w, sb);
+        return CxNewtonPoint{E.outer.c[0] - E.inner.c[0], E.outer.c[1] - E.inner.c[1], cx{0.0, 0.0}, E.rel, E.st};
+      },
+      [&](double k, cx w) {
+        const CxMatch<3> E = cx_eval<3>(P, variant, k, w, sb);
+        return CxNewtonPoint{E.outer.c[0] - E.inner.c[0], E.outer.c[1] - E.inner.c[1], E.outer.c[2] - E.inner.c[2], E.rel, E.st};
+      },
+      kv, gre, gim, i, cnt, max_iter, step_cap, max_shift, tol_percent, wre, wim, resid, dwdk, iters_out, flag_out);
 }
 
 }  // namespace

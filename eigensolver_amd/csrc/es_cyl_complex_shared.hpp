@@ -1,0 +1,181 @@
+// The complex-frequency evaluation of the untwisted cylinder (FAM_CYL0), written once over the scalar Z
+// (include/eigensolver_amd.h sections 14 and 15; the CPU restatements are tests/cyl_complex_model.py and
+// tests/cyl_complex_slope_model.py):
+//   Z = esb::cz        the plain complex value: es_cyl_complex.hip (determinant, roots)
+//   Z = esb::CJet<1>   value and d/d omega: the Newton steps of es_cyl_complex_slopes.hip
+//   Z = esb::CJet<2>   value, d/d omega and d/dk: the slopes
+// The wavenumber comes as K: a plain double where it is a constant of the differentiation (cz, CJet<1>), the jet (k, 0, 1)
+// for CJet<2>.
+//
+// Interior: the FAM_CYL0 formula text of es_shoot_device.hpp (make_entry, coef_pre, coef_finish, adjoint_start,
+// rk4_step_adjoint<0>, boundary_algebra) instantiated with Z, TRACK = false, the plain (not scaled, normalised) RK4 step, one
+// IEEE complex division per node.  Nothing of the coefficient formulas is restated here.
+// Exterior, written for the complex case (cyl_exterior): m_e and xi_e_const as exterior_cylinder, mu = principal sqrt(m_e),
+// K_n and I_n at complex argument (es_bessel_complex.hpp), the same far-field initial values and I-admixture.  The solution is
+// normalised by its own complex boundary value, P_e(boundary) = 1, where the real path divides by |P_v| and keeps the sign yb:
+// on the real axis D_c = yb D.
+// Every decision is taken on the value component: ES_PT_LEAKY where Re m_e < 0 (the rule of the slab's complex path, and of
+// the real path on the real axis; it keeps mu in the sector |arg mu| <= pi/4 the Bessel routines support); ES_PT_NONFINITE
+// where m_e, xi_e_const or the result is not finite -- in the jet instantiations a non-finite derivative of outer or inner
+// counts too; the branch on the gap of the two Bessel arguments; the sign of the boundary.  There is no continuum status: off
+// the real axis the coefficients have no zero on the grid; on it, callers have the real path (es_shoot_eval_*).
+// One (k, omega) point per lane; the base table is staged in LDS chunk by chunk (CH steps) and every lane forms its own
+// node entries.  Every lane of a workgroup makes every barrier call: lanes past the count march on dummy inputs and store
+// nothing.  Not on the benchmark path: written for clarity.
+#pragma once
+#include "es_cjet.hpp"
+#include "es_complex_roots.hpp"
+
+namespace es_cyl_complex_shared {
+using namespace es_complex_shared;
+using esb::cz;
+constexpr int FAM = FAM_CYL0;
+constexpr int NB = FamTraits<FAM>::NB;
+constexpr int NE = FamTraits<FAM>::NE;
+constexpr int CYLC_LDS_DOUBLES = NB * (2 * CH + 1);         // one chunk: nodes and mid-points of CH steps
+
+// what boundary_algebra reads of an exterior
+template <class Z> struct CylcExterior {
+  Z outer;           // xi_e = xi_e_const P_e'(boundary) / P_e(boundary)
+  double yb;         // P_e(boundary) after the normalisation: 1
+  Z Oe;              // (flow slab only)
+  int status;
+};
+
+template <class Z, class K> __device__ __forceinline__ CylcExterior<Z> cyl_exterior(const ShootDev& P, const K& k, const Z& w) {
+  CylcExterior<Z> X;
+  const K k2 = k * k;
+  const Z w2 = w * w;
+  X.Oe = w;
+  X.yb = 1.0;
+  X.outer = Z(cz(NAN, NAN));
+  const Z m_e = ((k2 * P.vAe2 - w2) * (k2 * P.ce2 - w2)) / (P.Se * (k2 * P.cTe2 - w2));       // CF:699
+  const Z cst = -1.0 / (P.rho_e * (k2 * P.vAe2 - w2));                                        // CF:702
+  if (val(m_e) < 0.0) { X.status = ES_PT_LEAKY; return X; }
+  if (!esb::cz_finite(value_of(m_e)) || !esb::cz_finite(value_of(cst))) { X.status = ES_PT_NONFINITE; return X; }
+  X.status = ES_PT_OK;
+  const Z mu = sqrt(m_e);
+  const double sgn = (P.xb < 0.0) ? -1.0 : 1.0;
+  const Z xR = mu * (P.R_factor / k), xb = mu;
+  const int n = P.m_ext;
+  const double dn = (double)n;
+  Z Kb, Kb1, KR, KR1;
+  cke_pair(n, xb, Kb, Kb1);
+  cke_pair(n, xR, KR, KR1);
+  const Z dKb = (dn / xb) * Kb - Kb1;                // e^z K_n'(z)
+  const Z dKR = (dn / xR) * KR - KR1;
+  const Z g = P.ic1 / (sgn * mu);
+  // P = a I + b K with (a, b) from the far-field values; common factor xR e^{xR - xb} dropped
+  Z Pv, dPv;
+  const Z gap = xR - xb;
+  if (val(gap) < 40.0) {
+    Z Ib, Ib1, IR, IR1;
+    cie_pair_from_k(n, xb, Kb, Kb1, Ib, Ib1);
+    cie_pair_from_k(n, xR, KR, KR1, IR, IR1);
+    const Z dIb = Ib1 + (dn / xb) * Ib;              // e^-z I_n'(z)
+    const Z dIR = IR1 + (dn / xR) * IR;
+    const Z a_s = -(P.ic0 * dKR - g * KR);
+    const Z b_s = -(g * IR - P.ic0 * dIR);
+    const Z E2 = exp(-2.0 * gap);
+    Pv = b_s * Kb + E2 * a_s * Ib;
+    dPv = (sgn * mu) * (b_s * dKb + E2 * a_s * dIb);
+  } else {
+    // I-admixture below e^-80: only the K part is left and b cancels in the normalisation
+    Pv = Kb;
+    dPv = (sgn * mu) * dKb;
+  }
+  X.outer = cst * (dPv / Pv);
+  if (!all_finite(X.outer)) X.status = ES_PT_NONFINITE;
+  return X;
+}
+
+// Copies the base table of the nst steps from step c0 on (2 nst + 1 points, point-major) into the LDS buffer `sb`, between two
+// barriers: every lane of the workgroup makes every call.
+__device__ __forceinline__ void cyl_stage_chunk(const ShootDev& P, int c0, int nst, double* __restrict__ sb) {
+  __syncthreads();
+#pragma unroll
+  for (int f = 0; f < NB; ++f)
+    for (int i = threadIdx.x; i < 2 * nst + 1; i += blockDim.x) sb[i * NB + f] = P.base[(size_t)f * P.npts + 2 * c0 + i];
+  __syncthreads();
+}
+
+// coefficients of the node whose base fields are at b
+template <class Z>
+__device__ __forceinline__ CoefT<Z> cyl_node(const ShootDev& P, const KScalT<Z>& s, const Z& w, const double* __restrict__ bn, Z* e) {
+  double b[NB], c[NE];
+#pragma unroll
+  for (int f = 0; f < NB; ++f) b[f] = bn[f];
+  make_entry<FAM, false>(b, s, e, c);
+  SignTrack trk;
+  CoefPreT<Z> C;
+  coef_pre<FAM, false>(e, c, P, s, w, C, trk);
+  CoefT<Z> A;
+  coef_finish<FAM>(C, 1.0 / C.den, A);
+  return A;
+}
+
+// The two sides of the matching condition at (k, w): D_c = outer - inner.  rel (percent) and st are formed from the values;
+// unless st == ES_PT_OK, outer and inner are not to be used and rel is NaN.
+template <class Z> struct CylcMatch {
+  Z outer, inner;
+  double rel;
+  uint8_t st;
+};
+
+// P carries bc_const at its true scale (the launches pass bc_const_raw).  Every lane of the workgroup must call this.
+template <class Z, class K>
+__device__ __forceinline__ CylcMatch<Z> cyl_shoot_point(const ShootDev& P, const K& k, const Z& w, double* __restrict__ sb) {
+  const KScalT<Z> s = make_kscal(P, Z(k));
+  const CylcExterior<Z> X = cyl_exterior<Z, K>(P, k, w);
+  const int nsteps = P.n_nodes - 1;
+  const double h = P.h, h2 = 0.5 * P.h, h6 = P.h / 6.0, h3 = P.h / 3.0;
+  Z e[NE];
+  CoefT<Z> B0;
+  Z zp(0.0), zq(0.0);
+  const int nchunks = (nsteps + CH - 1) / CH;
+  for (int c = nchunks - 1; c >= 0; --c) {
+    const int c0 = c * CH;
+    const int nst = (nsteps - c0 < CH) ? (nsteps - c0) : CH;
+    cyl_stage_chunk(P, c0, nst, sb);
+    if (c == nchunks - 1) {                            // last node: start vector of the march
+      B0 = cyl_node(P, s, w, sb + 2 * nst * NB, e);
+      adjoint_start<FAM>(P, B0, zp, zq);
+    }
+    for (int j = nst - 1; j >= 0; --j) {
+      const CoefT<Z> Bm = cyl_node(P, s, w, sb + (2 * j + 1) * NB, e);
+      const CoefT<Z> B1 = cyl_node(P, s, w, sb + (2 * j) * NB, e);
+      rk4_step_adjoint<FamTraits<FAM>::SHAPE>(zp, zq, B0, Bm, B1, h, h2, h6, h3);
+      B0 = B1;
+    }
+  }
+  // e: the entries of the boundary node (read by the slab branches of boundary_algebra only)
+  const MismatchT<Z> M = boundary_algebra<FAM>(P, s, w, X, zp, zq, e);
+  CylcMatch<Z> R;
+  R.outer = M.outer;
+  R.inner = M.inner;
+  R.st = (uint8_t)X.status;
+  const cz o = value_of(M.outer), in = value_of(M.inner), d = value_of(M.d);
+  const double sc = P.accept_norm ? esb::cz_abs(o) : fmax(esb::cz_abs(o), esb::cz_abs(in));
+  R.rel = esb::cz_abs(d) * 100.0 / sc;
+  if (X.status == ES_PT_OK && !(esb::cz_finite(d) && all_finite(M.outer) && all_finite(M.inner))) R.st = ES_PT_NONFINITE;
+  if (R.st != ES_PT_OK) R.rel = NAN;
+  return R;
+}
+
+inline int check_cyl_cx(es_context* ctx, const es_problem* prob) {
+  ES_REQUIRE(ctx, prob != nullptr, "null problem");
+  if (prob->dev.family != FAM_CYL0) {
+    ctx->last_error = "es_cyl_complex_* is implemented for ES_GEOM_CYLINDER problems only (the untwisted cylinder)";
+    return ES_ERR_UNSUPPORTED;
+  }
+  return ES_SUCCESS;
+}
+
+// the problem as the complex march takes it: z at its true scale, so the target of the axis condition as given
+inline ShootDev cyl_cx_dev(const es_problem* prob) {
+  ShootDev P = prob->dev;
+  P.bc_const = P.bc_const_raw;
+  return P;
+}
+
+}  // namespace es_cyl_complex_shared

@@ -1,23 +1,28 @@
-"""Complex frequencies on the untwisted cylinder (C ABI section 14 of include/eigensolver_amd.h): the determinant of the
+"""Complex frequencies on the untwisted cylinder (C ABI sections 14 and 15 of include/eigensolver_amd.h): the determinant of the
 shooting path at omega = omega_r + i omega_i on (k, Re omega, Im omega) grids and point lists, and the root search -- the
 unstable (Kelvin-Helmholtz) modes of a cylinder whose axial jet is fast enough, where the root leaves the real axis and
 ShootProblem.find_roots / trace_branches report nothing.
 
 For equilibrium.CylinderDensity and equilibrium.CylinderFlow, any azimuthal order m, "kink" and "sausage" axis conditions,
-both signs of r.  Shapes and return conventions are those of complex_flow.SlabComplexFlow.  DESIGN.md section 8i.
+both signs of r.  Shapes and return conventions are those of complex_flow.SlabComplexFlow.  Section 15 adds the exact slopes
+D_w, D_k of a root, Newton's iteration and `densify`, which turns a few unstable_roots rows into the growth-rate curve that
+postprocess.most_unstable reads.  DESIGN.md sections 8i and 8j.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from .complex_flow import _distinct
+from .complex_flow import ComplexTracing, _distinct
 from .shooting import ShootProblem, W_ABSOLUTE, W_PHASE_SPEED  # noqa: F401
 
 
-class CylinderComplex:
-    """D_c(k, omega) of one cylinder equilibrium at complex omega: grids, point lists, roots.  One ShootProblem per
-    (mode, m), created on first use."""
+class CylinderComplex(ComplexTracing):
+    """D_c(k, omega) of one cylinder equilibrium at complex omega: grids, point lists, roots, and through ComplexTracing
+    the slopes and the Newton tracing of section 15 -- root_slopes(mode, k, w, count=None, m=None), group_velocity(mode,
+    roots, count=None, m=None), newton(mode, k, w0, ..., m=None) and densify(mode, k, w, k_fine, shift_factor=4.0, m=None,
+    **newton_kw), with the return conventions of SlabComplexFlow.  One ShootProblem per (mode, m), created on first use."""
+    _SELECT = ("m",)
     P_TOL = 4.0                                     # acceptance of a refined root, percent: that of SlabComplexFlow
 
     def __init__(self, equilibrium, ctx=None):
@@ -37,6 +42,13 @@ class CylinderComplex:
         for p in self._problems.values():
             p.close()
         self._problems = {}
+
+    # ---- slopes and Newton tracing (C ABI section 15): ComplexTracing over these two calls ----------------------------------
+    def _slopes_call(self, p, *args):
+        return self.ctx.lib.es_cyl_complex_root_slopes(self.ctx.handle, p.handle, *args)
+
+    def _newton_call(self, p, *args):
+        return self.ctx.lib.es_cyl_complex_newton(self.ctx.handle, p.handle, *args)
 
     # ---- evaluation ------------------------------------------------------------------------------------------------
     def eval_grid(self, mode, k, w_re, w_im, w_mode=W_ABSOLUTE, m=None):

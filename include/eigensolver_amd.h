@@ -1015,6 +1015,57 @@ int es_cyl_complex_find_roots(es_context* ctx, const es_problem* prob, const dou
                               const double* d_D_re, const double* d_D_im, const uint8_t* d_status, int n_iter,
                               double tol_percent, es_complex_root_table* table, int* out_count);
 
+/* ======================================================================================================
+ * (15) Slopes and Newton tracing of complex roots of the untwisted cylinder (the unstable modes of section 14): what section
+ *     12 is to section 6.  D_c(k, omega) of es_cyl_complex_eval_points is holomorphic in omega; with D_w = dD_c/d omega and
+ *     D_k = dD_c/dk (k real)
+ *       d omega / dk = -D_k / D_w:  the real part is the group speed, the imaginary part the slope of the growth rate,
+ *                                   whose zero marks the most unstable wavenumber;
+ *       -D_c / D_w              :  the Newton correction, quadratic because D_c is holomorphic (section 14 takes 12 secant
+ *                                   steps from a cell centre, plus the grid row that found the cell).
+ *     Both calls take the problem as section 14 does: ES_GEOM_CYLINDER only, every other geometry -- the twisted cylinder,
+ *     which is still not offered at complex frequency, and the slabs -- gets ES_ERR_UNSUPPORTED.  Both are asynchronous on the
+ *     context's stream with no host read-back; n == 0 succeeds and touches nothing (the arrays may then be NULL).  d_count
+ *     (may be NULL): as in sections 10 - 13 -- the kernels use min(max(*d_count, 0), n) and leave entries beyond it alone.
+ *
+ *     es_cyl_complex_root_slopes: one (k, omega) pair per lane; the node entries, the coefficients, the adjoint RK4 march,
+ *     the Bessel exterior and the boundary algebra of section 14 -- the same program text -- carried in jets of three complex
+ *     components (value, d/d omega, d/dk); K_n and I_n carry their argument derivative by the recurrence identities.  Exact
+ *     to rounding, no step to choose.
+ *       d_outer / d_inner [3][n][2]: (re, im) pairs; row 0 the value, row 1 d/d omega, row 2 d/dk of xi_e and xi_i.  Row 0
+ *         is the outer and inner of es_cyl_complex_eval_points, the section-14 value; D_w and D_k are the differences of
+ *         rows 1 and 2.  The rows are n apart, whatever d_count holds.
+ *       d_status [n]: the status section 14 gives the pair; ES_PT_NONFINITE also where a derivative of outer or inner is
+ *         not finite.  A pair whose status is not ES_PT_OK gets NaN in all six outputs; the other pairs do not depend on it.
+ *     Any of the three output pointers may be NULL: that output is skipped.
+ *     ES_ERR_INVALID_ARG: n < 0, a null problem, d_k, d_w_re or d_w_im null with n > 0.
+ *
+ *     es_cyl_complex_newton: one guess per lane, the iteration of es_complex_newton (section 12) step for step, with
+ *         resid = the rel of section 14 at the final w: 100 |D_c| / max(|outer|, |inner|), |outer| alone for problems with
+ *         accept_norm.
+ *       d_w_re, d_w_im, d_resid, d_iters, d_flag [n]; d_dwdk [n][2] (re, im; may be NULL).  w is reported whatever the flag;
+ *       resid and dwdk are NaN where the final status is not ES_PT_OK.  max_iter == 0 is the final evaluation alone: the
+ *       guess with its resid and slope.  Pass DBL_MAX for no step_cap / max_shift.
+ *       At a branch point -- where a conjugate pair of roots meets on the real axis, the onset of the instability --
+ *       D_w = 0: dwdk is then not finite and the iteration stops with ok = false if it lands there exactly; nothing else is
+ *       done about it.  On the real axis d omega / dk is real: the group speed of section 11.
+ *     ES_ERR_INVALID_ARG: n < 0, max_iter < 0, step_cap, max_shift or tol_percent not positive, a null problem, any array
+ *     but d_count and d_dwdk null with n > 0.
+ *     Not offered: the twisted cylinder, eigenfunctions and fields at complex cylinder roots, second derivatives.
+ * ====================================================================================================== */
+int es_cyl_complex_root_slopes(es_context* ctx, const es_problem* prob,
+                               const double* d_k, const double* d_w_re, const double* d_w_im, int n,
+                               const int32_t* d_count /* may be NULL */,
+                               double* d_outer /* [3][n][2]: value, d/dw, d/dk; (re, im) pairs */,
+                               double* d_inner /* [3][n][2] */, uint8_t* d_status);
+
+int es_cyl_complex_newton(es_context* ctx, const es_problem* prob,
+                          const double* d_k, const double* d_guess_re, const double* d_guess_im, int n,
+                          const int32_t* d_count /* may be NULL */,
+                          int max_iter, double step_cap, double max_shift, double tol_percent,
+                          double* d_w_re, double* d_w_im, double* d_resid,
+                          double* d_dwdk /* [n][2], may be NULL */, int32_t* d_iters, int32_t* d_flag);
+
 #ifdef __cplusplus
 }
 #endif
