@@ -80,7 +80,8 @@ def _probe_needs_build():
     if not os.path.exists(LIB_PROBE):
         return True
     t = os.path.getmtime(LIB_PROBE)
-    return any(os.path.getmtime(s) > t for s in (PROBE_SRC, os.path.join(CSRC, "es_bessel.hpp")))
+    headers = ("es_bessel.hpp", "es_bessel_complex.hpp", "es_cjet.hpp")
+    return any(os.path.getmtime(s) > t for s in (PROBE_SRC,) + tuple(os.path.join(CSRC, h) for h in headers))
 
 
 def _build_probe(verbose):

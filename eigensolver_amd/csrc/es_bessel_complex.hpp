@@ -12,13 +12,25 @@
 //                then the upward recurrence K_{n+1} = K_{n-1} + (2n/z) K_n (K dominant for Re z > 0: stable).
 //   * I_n, I_{n+1}: Miller's backward recurrence for the ratio and the Wronskian I_n K_{n+1} + I_{n+1} K_n = 1/z for the
 //                normalisation (esb::ie_pair_from_k); |z| < 0.5: the ascending series.
-// Accuracy, host build against scipy.special.kve / ive (AMOS) on orders 0 ... 11, |z| in [1e-3, 300], arg z in
-// {-pi/4, 0, pi/8, pi/4} with points packed around |z| = 2 and |z| = 0.5 (tests/test_hostmath_complex.py), worst relative
-// error |f - f_ref| / |f_ref|:
-//   e^z K_n, K_{n+1}    4.9e-15, at z = 1.98: just under |z| = 2 the series of K_0 subtracts terms 12 times the result
-//   e^-z I_n, I_{n+1}   1.9e-14, at order 9, |z| = 0.004: the reference's own error -- against mpmath at 40 digits
-//                       this header is within 3e-16 there (and at every point looked at), scipy 1.9e-14; |z| >= 0.5: 9.3e-15
-// scipy is itself a few ulp off, so these are upper estimates.  The test holds the host build to twice these figures.
+// Accuracy against correctly rounded values (tests/golden/bessel_complex_truth.npz: mpmath at 40 digits; orders 0, 1, 2, 3, 5,
+// 10, 11, 20, 40; arg z in {-pi/4, -pi/8, -1e-3, 0, 1e-9, pi/16, pi/8, 3pi/16, pi/4}; 36 radii log-spaced over [1e-6, 700],
+// 0.5 and 2 with the doubles 1 and 4 ulp to either side, 1.98, 2.02, and 3e3, 3e4 apart), worst error relative to |f| in
+// u = 2^-52 = 2.2e-16, host build (tests/test_hostmath_complex.py::test_truth_complex):
+//   e^z K_n, K_{n+1}    |z| <= 700: 32 u (7.1e-15) at n = 0, z = 2 e^{-0.001 i}: at |z| = 2 the series of K_0 subtracts terms
+//                       12 times the result; 24 u at n = 1, 14 ... 16 u at n = 2 ... 11, 22 u at n = 20, 42 u (9.2e-15) at
+//                       n = 40 (the upward recurrence, |z| = 0.06);  |z| = 3e3, 3e4: 3.5 u
+//   e^-z I_n, I_{n+1}   |z| <= 700: 14 ... 16 u for n <= 11 at |z| = 1.98 (it inherits the error of K), 21 u at n = 20, 38 u
+//                       at n = 40 (|z| = 0.5, arg z = -pi/4);  |z| = 3e3, 3e4: 4.4 u (1350 u at n = 0, |z| = 3e4,
+//                       arg z = -pi/4 while Miller's start index was sized by |z|: see cie_pair_from_k)
+//   d/dz of either      (CJet of es_cjet.hpp) relative to (|f_n| + |f_{n+1}|)(1 + (n + 1)/|z|), the terms of the
+//                       identities: 13 u at n = 0, 42 u at n = 40 for K; 2 u at n = 0, 35 u at n = 40 for I
+// The device build (gfx950: __constant__ reciprocal tables, qdiv past index 64 of CF2, the device exp / log / hypot / atan2 /
+// sin / cos) has its worst error per order within 1.1 u of these (14.7 u against 13.7 u at n = 10; equal at n = 0, 1, 40),
+// with the same bits per row whether the order is wave-uniform or every lane runs its own order and branch
+// (tests/test_devmath_gpu.py, which records the table).  The primitives cz_sqrt,
+// cz_log, cz_exp and the two divisions are within 1.5 u of the modulus of the result on host and device, the sign on the
+// cut of sqrt and log following the sign of the zero.  scipy.special.kve / ive is itself up to 1.9e-14 off (I at order 9,
+// |z| = 0.004); the comparison with it stays as a second, independent reference.
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -175,12 +187,18 @@ ES_HD void cie_pair(int n, cz z, cz& in_, cz& inp1) {
 
 // scaled I_n, I_{n+1} from the scaled K_n, K_{n+1} at the same argument: Miller's backward recurrence for the ratio
 // I_{n+1} / I_n (I is the minimal solution for Re z > 0), the Wronskian for the normalisation.  The start index follows
-// esb::ie_pair_from_k with |z| for x; |z| is capped there so that an argument the caller never meant (an iterate that ran
-// away) costs a bounded number of steps.
+// esb::ie_pair_from_k with |z|^2 / Re z for x: the error of the arbitrary start decays like exp(-M^2 Re z / |z|^2), so this,
+// not |z|, is what M^2 = 40 x has to cover.  It is |z| on the real axis, bit for bit (hypot(x, 0) = x and x / x = 1: M as
+// before), and at most sqrt 2 |z| in the sector.  Sized by |z| alone the decay at arg z = +-pi/4 was exp(-28), and
+// the additive terms of M stop helping as |z| grows: at |z| = 3e4, arg z = -pi/4 the host build was 1350 u off at n = 0,
+// 801 u at n = 10, 169 u at n = 40 (u = 2^-52, against mpmath), and the z-derivative 9.8 u at |z| = 391; now 4.4 u at
+// worst on |z| = 3e3 and 3e4, every order and angle, as for |z| <= 700, and the derivative 2.1 u.  The quantity is capped so
+// that an argument the caller never meant (an iterate that ran away, Re z <= 0 or not a number) costs a bounded number of
+// steps.
 ES_HD void cie_pair_from_k(int n, cz z, cz kn, cz knp1, cz& in_, cz& inp1) {
   const double az = cz_abs(z);
   if (az < 0.5) { cie_pair(n, z, in_, inp1); return; }
-  const int M = n + 10 + (int)sqrt(40.0 * fmin(az, 1.0e6));
+  const int M = n + 10 + (int)sqrt(40.0 * fmin(az * fabs(az / z.re), 1.0e6));
   const cz toz = 2.0 / z;
   cz ip(0.0), ic(1.0);                                        // I_{M+1}, I_M up to a common factor, kept within range
   for (int k = M; k > n; --k) {                               // (ip, ic) = (I_{k+1}, I_k) -> (I_k, I_{k-1})
