@@ -333,4 +333,11 @@ def _sig(lib):
     if hasattr(lib, "es_cyl_complex_root_slopes"):          # likewise
         lib.es_cyl_complex_root_slopes.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, vp, vp]
         lib.es_cyl_complex_newton.argtypes = [vp, vp, vp, vp, vp, i, vp, i, d, d, d, vp, vp, vp, vp, vp, vp]
+    # (16) eigenfunctions and perturbation fields of complex cylinder roots
+    if hasattr(lib, "es_cyl_complex_eigenfunction"):        # likewise
+        lib.es_cyl_complex_eigenfunction.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, i, vp, vp, vp, vp]
+        lib.es_cyl_complex_polarisation.argtypes = [vp, vp, vp, vp, i, i, vp, vp, i, vp, vp, vp, C.POINTER(FieldProfiles), i,
+                                                    d, d, d, d, i, vp, vp]
+        lib.es_cyl_complex_field_synthesis.argtypes = [vp, vp, vp, i, i, d, d, d, vp, i, vp, i, vp, i, C.c_uint32, d, i, vp,
+                                                       vp]
     return lib

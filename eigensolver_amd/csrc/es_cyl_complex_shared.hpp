@@ -42,21 +42,34 @@ template <class Z> struct CylcExterior {
   int status;
 };
 
-template <class Z, class K> __device__ __forceinline__ CylcExterior<Z> cyl_exterior(const ShootDev& P, const K& k, const Z& w) {
-  CylcExterior<Z> X;
+// The exterior solution itself, before the boundary ratio is taken: what cyl_exterior reduces to xi_e and the eigenfunction
+// kernel of es_cyl_complex_eigen.hip evaluates at every exterior point.  Up to the common factor dropped below,
+//   P_e(x) = [b_s Ke_n(mu |x|) + e^{-2 (xR - mu |x|)} a_s Ie_n(mu |x|)] e^{-(mu |x| - xb)},     P_e(boundary) = Pv;
+// with `near` false the I part is dropped (a_s is not formed, b_s = 1).  Fields past `status` are set only for ES_PT_OK.
+template <class Z> struct CylcExteriorSolution {
+  int status;        // ES_PT_OK, ES_PT_LEAKY or ES_PT_NONFINITE by m_e and xi_e_const alone
+  bool near;         // Re(xR - xb) < 40: the I-admixture is kept
+  double sgn;        // sign of the boundary radius
+  Z cst;             // xi_e_const
+  Z mu, xR, xb;      // principal sqrt(m_e); the Bessel arguments of the far field and the boundary
+  Z a_s, b_s;
+  Z Pv, dPv;         // P_e and dP_e/dr at the boundary
+};
+
+template <class Z, class K>
+__device__ __forceinline__ CylcExteriorSolution<Z> cyl_exterior_solution(const ShootDev& P, const K& k, const Z& w) {
+  CylcExteriorSolution<Z> S;
   const K k2 = k * k;
   const Z w2 = w * w;
-  X.Oe = w;
-  X.yb = 1.0;
-  X.outer = Z(cz(NAN, NAN));
   const Z m_e = ((k2 * P.vAe2 - w2) * (k2 * P.ce2 - w2)) / (P.Se * (k2 * P.cTe2 - w2));       // CF:699
-  const Z cst = -1.0 / (P.rho_e * (k2 * P.vAe2 - w2));                                        // CF:702
-  if (val(m_e) < 0.0) { X.status = ES_PT_LEAKY; return X; }
-  if (!esb::cz_finite(value_of(m_e)) || !esb::cz_finite(value_of(cst))) { X.status = ES_PT_NONFINITE; return X; }
-  X.status = ES_PT_OK;
+  S.cst = -1.0 / (P.rho_e * (k2 * P.vAe2 - w2));                                              // CF:702
+  if (val(m_e) < 0.0) { S.status = ES_PT_LEAKY; return S; }
+  if (!esb::cz_finite(value_of(m_e)) || !esb::cz_finite(value_of(S.cst))) { S.status = ES_PT_NONFINITE; return S; }
+  S.status = ES_PT_OK;
   const Z mu = sqrt(m_e);
   const double sgn = (P.xb < 0.0) ? -1.0 : 1.0;
   const Z xR = mu * (P.R_factor / k), xb = mu;
+  S.mu = mu; S.sgn = sgn; S.xR = xR; S.xb = xb;
   const int n = P.m_ext;
   const double dn = (double)n;
   Z Kb, Kb1, KR, KR1;
@@ -66,9 +79,9 @@ template <class Z, class K> __device__ __forceinline__ CylcExterior<Z> cyl_exter
   const Z dKR = (dn / xR) * KR - KR1;
   const Z g = P.ic1 / (sgn * mu);
   // P = a I + b K with (a, b) from the far-field values; common factor xR e^{xR - xb} dropped
-  Z Pv, dPv;
   const Z gap = xR - xb;
-  if (val(gap) < 40.0) {
+  S.near = val(gap) < 40.0;
+  if (S.near) {
     Z Ib, Ib1, IR, IR1;
     cie_pair_from_k(n, xb, Kb, Kb1, Ib, Ib1);
     cie_pair_from_k(n, xR, KR, KR1, IR, IR1);
@@ -77,14 +90,27 @@ template <class Z, class K> __device__ __forceinline__ CylcExterior<Z> cyl_exter
     const Z a_s = -(P.ic0 * dKR - g * KR);
     const Z b_s = -(g * IR - P.ic0 * dIR);
     const Z E2 = exp(-2.0 * gap);
-    Pv = b_s * Kb + E2 * a_s * Ib;
-    dPv = (sgn * mu) * (b_s * dKb + E2 * a_s * dIb);
+    S.a_s = a_s; S.b_s = b_s;
+    S.Pv = b_s * Kb + E2 * a_s * Ib;
+    S.dPv = (sgn * mu) * (b_s * dKb + E2 * a_s * dIb);
   } else {
     // I-admixture below e^-80: only the K part is left and b cancels in the normalisation
-    Pv = Kb;
-    dPv = (sgn * mu) * dKb;
+    S.a_s = Z(cz(0.0, 0.0)); S.b_s = Z(cz(1.0, 0.0));
+    S.Pv = Kb;
+    S.dPv = (sgn * mu) * dKb;
   }
-  X.outer = cst * (dPv / Pv);
+  return S;
+}
+
+template <class Z, class K> __device__ __forceinline__ CylcExterior<Z> cyl_exterior(const ShootDev& P, const K& k, const Z& w) {
+  CylcExterior<Z> X;
+  X.Oe = w;
+  X.yb = 1.0;
+  X.outer = Z(cz(NAN, NAN));
+  const CylcExteriorSolution<Z> S = cyl_exterior_solution<Z, K>(P, k, w);
+  X.status = S.status;
+  if (S.status != ES_PT_OK) return X;
+  X.outer = S.cst * (S.dPv / S.Pv);
   if (!all_finite(X.outer)) X.status = ES_PT_NONFINITE;
   return X;
 }

@@ -94,14 +94,15 @@ __device__ __forceinline__ void finish_point(const ShootDev& P, const Mismatch& 
   if (crossed) st = ES_PT_CONTINUUM;
 }
 
-// forward RK4 step of one state vector (u, v):  y' = A y  (interior_rows of es_interior_march.hpp)
-template <bool DIAG>
-__device__ __forceinline__ void rk4_step_forward(double& u, double& v, const Coef& A0, const Coef& Am, const Coef& A1,
-                                                 double h, double h2, double h6, double h3) {
+// forward RK4 step of one state vector (u, v):  y' = A y  (interior_rows of es_interior_march.hpp: Num = double; the complex
+// eigenfunction march of es_cyl_complex_eigen.hip: Num = esb::cz)
+template <bool DIAG, class Num>
+__device__ __forceinline__ void rk4_step_forward(Num& u, Num& v, const CoefT<Num>& A0, const CoefT<Num>& Am,
+                                                 const CoefT<Num>& A1, double h, double h2, double h6, double h3) {
 #define ES_RHS_F(A, uu, vv, ku, kv)                                              \
   if (DIAG) { ku = fma(A.a11, uu, A.a12 * vv); kv = fma(A.a22, vv, A.a21 * uu); } \
   else      { ku = A.a12 * vv;                 kv = A.a21 * uu; }
-  double k1u, k1v, k2u, k2v, k3u, k3v, k4u, k4v, tu, tv;
+  Num k1u, k1v, k2u, k2v, k3u, k3v, k4u, k4v, tu, tv;
   ES_RHS_F(A0, u, v, k1u, k1v);
   tu = fma(h2, k1u, u); tv = fma(h2, k1v, v);
   ES_RHS_F(Am, tu, tv, k2u, k2v);

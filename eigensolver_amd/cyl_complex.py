@@ -6,7 +6,9 @@ ShootProblem.find_roots / trace_branches report nothing.
 For equilibrium.CylinderDensity and equilibrium.CylinderFlow, any azimuthal order m, "kink" and "sausage" axis conditions,
 both signs of r.  Shapes and return conventions are those of complex_flow.SlabComplexFlow.  Section 15 adds the exact slopes
 D_w, D_k of a root, Newton's iteration and `densify`, which turns a few unstable_roots rows into the growth-rate curve that
-postprocess.most_unstable reads.  DESIGN.md sections 8i and 8j.
+postprocess.most_unstable reads.  Section 16 adds what the mode looks like: `eigenfunction` (P and xi_r at complex roots),
+`polarisation` (the seven complex amplitudes) and `fields` (growing float32 frames ready for postprocess.write_vtk_frames).
+DESIGN.md sections 8i, 8j and 8k.
 """
 import ctypes as C
 
@@ -14,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from .complex_flow import ComplexTracing, _distinct
-from .shooting import ShootProblem, W_ABSOLUTE, W_PHASE_SPEED  # noqa: F401
+from .shooting import ShootProblem, W_ABSOLUTE, W_PHASE_SPEED, _frame_chunks, _frames_out, var_mask  # noqa: F401
 
 
 class CylinderComplex(ComplexTracing):
@@ -127,3 +129,97 @@ class CylinderComplex(ComplexTracing):
         ok = roots["flag"].cpu().numpy() == 1
         w, row = roots["w"].cpu().numpy()[ok], roots["row"].cpu().numpy()[ok]
         return [_distinct(w[row == r]) for r in range(len(k))]
+
+    # ---- eigenfunctions and perturbation fields (C ABI section 16) -----------------------------------------------------
+    def eigenfunction(self, mode, k, w, n_ext=500, m=None):
+        """Two-region solution at the complex (k, omega) pairs (es_cyl_complex_eigenfunction).  `w` is complex and `k` is
+        broadcast against it; both may be tensors, e.g. roots["k"], roots["w"] of find_roots.  Dict of CUDA tensors as
+        SlabComplexFlow.eigenfunction: x_int [N], value_int / flux_int [n, N] (complex128: P and xi_r on the node grid, node 0 =
+        boundary), x_ext [n, n_ext], value_ext / flux_ext [n, n_ext] (complex128, far field to boundary), status [n] (uint8,
+        that of eval_points; rows that are not ES_PT_OK are NaN).  Scaled per unit P_e(boundary): value_ext[:, -1] = 1,
+        value_int[:, 0] = 1 and flux_ext[:, -1] - flux_int[:, 0] = D_c."""
+        import torch
+        p, dk, dre, dim = self._pairs(mode, k, w, m=m)
+        dev = dk.device
+        n, N, n_ext = dk.numel(), int(p.desc.n_nodes), int(n_ext)
+        vi = torch.empty((n, N), dtype=torch.complex128, device=dev)
+        fi = torch.empty((n, N), dtype=torch.complex128, device=dev)
+        xe = torch.empty((n, n_ext), dtype=torch.float64, device=dev)
+        ve = torch.empty((n, n_ext), dtype=torch.complex128, device=dev)
+        fe = torch.empty((n, n_ext), dtype=torch.complex128, device=dev)
+        st = torch.empty(n, dtype=torch.uint8, device=dev)
+        rc = self.ctx.lib.es_cyl_complex_eigenfunction(self.ctx.handle, p.handle, _lib.ptr(dk), _lib.ptr(dre), _lib.ptr(dim), n,
+                                                       _lib.ptr(vi), _lib.ptr(fi), n_ext, _lib.ptr(xe), _lib.ptr(ve),
+                                                       _lib.ptr(fe), _lib.ptr(st))
+        _lib.check(self.ctx.handle, rc)
+        x_int = torch.linspace(p.desc.x_boundary, p.desc.x_end, N, dtype=torch.float64, device=dev)
+        return dict(x_int=x_int, value_int=vi, flux_int=fi, x_ext=xe, value_ext=ve, flux_ext=fe, status=st)
+
+    def polarisation(self, mode, k, w, n_ext=500, reference_quirks=True, m=None):
+        """Complex radial amplitudes of the modes at the complex (k, omega) pairs (es_cyl_complex_polarisation on the arrays
+        of `eigenfunction`): dict of CUDA tensors radius [n, N + n_ext], amp [n, 7, N + n_ext] (complex128, channels
+        _lib.AMP_NAMES, on the grid of ShootProblem.polarisation) and status [n].  The amplitudes are the analytic
+        continuation in omega of ShootProblem.polarisation's: every field is Re[amp Theta(theta) e^{i (k z - w t)}] with
+        section 7's angular factors.  Rows that are not ES_PT_OK are NaN.  Positive radii (r_sign=+1) only."""
+        import torch
+        p = self.problem(mode, m)
+        p._require_positive_cylinder()
+        e = self.eigenfunction(mode, k, w, n_ext=n_ext, m=m)
+        _, dk, dre, dim = self._pairs(mode, k, w, m=m)
+        n, N, n_ext = dk.numel(), int(p.desc.n_nodes), int(n_ext)
+        prof = {a: p._dev(b) for a, b in p.field_profiles(reference_quirks).items()}
+        fp = _lib.FieldProfiles(*[prof[a].data_ptr() for a in _lib._FIELD_PROFILE_FIELDS])
+        radius = torch.empty((n, N + n_ext), dtype=torch.float64, device=dk.device)
+        amp = torch.empty((n, 7, N + n_ext), dtype=torch.complex128, device=dk.device)
+        d = p.desc
+        rc = self.ctx.lib.es_cyl_complex_polarisation(self.ctx.handle, _lib.ptr(dk), _lib.ptr(dre), _lib.ptr(dim), n, N,
+                                                      _lib.ptr(e["value_int"]), _lib.ptr(e["flux_int"]), n_ext,
+                                                      _lib.ptr(e["x_ext"]), _lib.ptr(e["value_ext"]), _lib.ptr(e["flux_ext"]),
+                                                      C.byref(fp), int(d.m), d.rho_e, d.vA_e, d.c_e, d.cT_e,
+                                                      _lib.FIELD_REFERENCE if reference_quirks else 0, _lib.ptr(radius),
+                                                      _lib.ptr(amp))
+        _lib.check(self.ctx.handle, rc)
+        return dict(radius=radius, amp=amp, status=e["status"])
+
+    def field_synthesis(self, radius, amp, m, k, w, theta, z, t, variables=None, v_scale=1.0, flags=0, want_points=True,
+                        out=None):
+        """es_cyl_complex_field_synthesis for the amplitude table of one mode (radius [n_r] float64, amp [7, n_r] complex128,
+        CUDA; w complex): float32 frames out[n_t, n_sel, n_z, n_theta, n_r] and, with want_points, points[n_z, n_theta, n_r, 3],
+        as shooting.field_synthesis.  Returns (out, points, names)."""
+        import torch
+        mask, names = var_mask(variables)
+        n_r, n_theta, n_z, n_t = radius.numel(), theta.numel(), z.numel(), t.numel()
+        assert amp.shape == (7, n_r) and amp.dtype == torch.complex128 and amp.is_contiguous() and radius.dtype == torch.float64
+        out = _frames_out(out, (n_t, len(names), n_z, n_theta, n_r), radius.device)
+        pts = torch.empty((n_z, n_theta, n_r, 3), dtype=torch.float32, device=radius.device) if want_points else None
+        w = complex(w)
+        rc = self.ctx.lib.es_cyl_complex_field_synthesis(self.ctx.handle, _lib.ptr(radius), _lib.ptr(amp), n_r, int(m), float(k),
+                                                         w.real, w.imag, _lib.ptr(theta), n_theta, _lib.ptr(z), n_z,
+                                                         _lib.ptr(t), n_t, mask, float(v_scale), int(flags),
+                                                         _lib.ptr(pts) if want_points else None, _lib.ptr(out))
+        _lib.check(self.ctx.handle, rc)
+        return out, pts, names
+
+    def fields(self, mode, k, w, theta, z, t, variables=None, v_scale=1.0, big_endian=False, frames_per_call=None, n_ext=500,
+               reference_quirks=True, m=None):
+        """Perturbation fields of ONE complex root (k, omega) on the mesh (r, theta, z, t), the growth factor e^{Im w t}
+        included: the dict of ShootProblem.fields -- points [n_z, n_theta, n_r, 3], t [n_t], names, frames [n_t, n_sel, n_z,
+        n_theta, n_r], <name>: frames[:, i], float32 CUDA tensors in VTK's point order -- or with frames_per_call the generator
+        of such dicts; the points are produced once.  big_endian: ready for postprocess.write_vtk_frames."""
+        p = self.problem(mode, m)
+        p._require_positive_cylinder()
+        if np.ndim(k) != 0 or np.ndim(w) != 0:
+            raise ValueError("fields() takes one root: scalar k and omega")
+        k, w = float(k), complex(w)
+        mask, names = var_mask(variables)
+        pol = self.polarisation(mode, [k], [w], n_ext=n_ext, reference_quirks=reference_quirks, m=m)
+        radius, amp = pol["radius"][0], pol["amp"][0]
+        dth, dz, dt = (p._dev(a).reshape(-1) for a in (theta, z, t))
+        flags = (_lib.FIELD_Z_REFERENCE_ANGLE if reference_quirks else 0) | (_lib.FIELD_BIG_ENDIAN if big_endian else 0)
+
+        def synth(t_part, carry):                     # the points are produced once and handed to the later chunks
+            out, pts, _ = self.field_synthesis(radius, amp, int(p.desc.m), k, w, dth, dz, t_part, names, v_scale, flags,
+                                               want_points=carry is None)
+            return out, carry or dict(points=pts)
+
+        return _frame_chunks(synth, dt, frames_per_call, names)

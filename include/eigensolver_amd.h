@@ -1051,7 +1051,7 @@ int es_cyl_complex_find_roots(es_context* ctx, const es_problem* prob, const dou
  *       done about it.  On the real axis d omega / dk is real: the group speed of section 11.
  *     ES_ERR_INVALID_ARG: n < 0, max_iter < 0, step_cap, max_shift or tol_percent not positive, a null problem, any array
  *     but d_count and d_dwdk null with n > 0.
- *     Not offered: the twisted cylinder, eigenfunctions and fields at complex cylinder roots, second derivatives.
+ *     Not offered: the twisted cylinder, second derivatives.  (Eigenfunctions and fields at complex roots: section 16.)
  * ====================================================================================================== */
 int es_cyl_complex_root_slopes(es_context* ctx, const es_problem* prob,
                                const double* d_k, const double* d_w_re, const double* d_w_im, int n,
@@ -1065,6 +1065,77 @@ int es_cyl_complex_newton(es_context* ctx, const es_problem* prob,
                           int max_iter, double step_cap, double max_shift, double tol_percent,
                           double* d_w_re, double* d_w_im, double* d_resid,
                           double* d_dwdk /* [n][2], may be NULL */, int32_t* d_iters, int32_t* d_flag);
+
+/* ======================================================================================================
+ * (16) Eigenfunctions and perturbation fields of complex cylinder roots (the unstable modes of sections 14 and 15): what
+ *     sections 5 and 7 are to section 2 -- P(r), xi_r(r), the seven amplitudes and growing float32 frames for VTK.
+ *     es_cyl_complex_eigenfunction takes the problem as sections 14 / 15 do: ES_GEOM_CYLINDER only, every other geometry gets
+ *     ES_ERR_UNSUPPORTED.  DESIGN.md section 8k.
+ *
+ *     es_cyl_complex_eigenfunction: the signature of es_complex_eigenfunction (section 6) without `variant`, the layout of
+ *     section 5: interior node 0 is the boundary; the exterior runs from the far field to the boundary on
+ *     linspace(-/+R, -/+1, n_ext) with the last point exactly -/+1 (both signs of r are accepted).  value = P, flux = xi_r:
+ *     inside xi_r = Xi / r, outside xi_r = xi_e_const P_e'.  Complex arrays are interleaved (re, im) pairs.
+ *       Interior: the algorithm of section 5 for cylinders in complex arithmetic.  Both RK4 marches run from the axis node
+ *       outwards on the node / mid-point coefficient sets of section 14 (one complex division per node): the first carries
+ *       the columns e = (1, 0) and d to the boundary -- ES_AXIS_KINK: d = (0, 1), target = bc_const xi_e; ES_AXIS_SAUSAGE:
+ *       d = (a12, -a11), target = 0 --, beta follows from P(r_b) = P_b, the second march writes every node from the axis
+ *       state target e + beta d.
+ *       Exterior: P_e(x) = [b_s K_m(mu |x|) + E2x a_s I_m(mu |x|)] e^{-(mu |x| - mu)} / Pv with the scaled Bessel functions,
+ *       a_s, b_s and Pv of section 14, mu the principal square root; where Re(xR - xb) >= 40 the I part is dropped at every
+ *       point, as section 14 drops it at the boundary.
+ *       Normalisation: that of section 14, P_e(boundary) = 1 + 0i.  So the exterior value at the boundary is exactly 1, the
+ *       interior value at node 0 is 1 to rounding (beta imposes it), the exterior flux at the boundary is the `outer` of
+ *       es_cyl_complex_eval_points, and
+ *           exterior flux at the boundary - interior flux at node 0 = D_c.
+ *       The outward RK4 step and the adjoint RK4 step of the determinant are transposes of each other step by step, so this
+ *       holds to rounding (2e-15 of max(|outer|, |inner|) measured), not only to truncation as in section 5.
+ *       d_status[i] (may be NULL) is the status section 14 gives the pair: ES_PT_OK, ES_PT_LEAKY or ES_PT_NONFINITE.  A pair
+ *       that is not ES_PT_OK gets NaN in every value and flux entry; its d_ext_x row is still written and the other pairs do
+ *       not depend on it.  n_ext is 0 or >= 2; n == 0 succeeds and touches nothing.  Asynchronous on the context's stream
+ *       (with d_status = NULL the first call at a larger n grows the context's scratch, which synchronises).  Argument errors
+ *       as in section 6.
+ *
+ *     es_cyl_complex_polarisation: the interior and exterior formulas of es_cyl_polarisation (section 7) -- one program text
+ *     -- evaluated with complex omega (d_w_re, d_w_im [n]), P and xi_r (the arrays of es_cyl_complex_eigenfunction).  The same
+ *     es_field_profiles, ES_FIELD_REFERENCE and output order: n_r = N + n_ext, axis node -> boundary, then boundary -> far
+ *     field, the boundary radius twice; radii must be positive.  d_radius [n x n_r] real; d_amp is complex,
+ *     d_amp[((i * 7 + c) * n_r + j) * 2 + {re, im}], channels ES_AMP_*.  NaN eigenfunction rows give complex-NaN amplitudes;
+ *     nodes where Om^2 - omega_A^2 or Om^2 - omega_c^2 vanish are not guarded, as in section 7.
+ *       Phase convention: the convention between the channels is section 7's, which is the reference's -- the amplitudes are
+ *       the analytic continuation of section 7 in omega, no factor of i is introduced between xi_r and xi_phi, xi_z.
+ *
+ *     es_cyl_complex_field_synthesis: the complex amplitude table of ONE mode (d_amp [7 x n_r x 2]) -> float32 frames
+ *     d_out [n_t][n_sel][n_z][n_theta][n_r]; arguments as es_cyl_field_synthesis with w_re, w_im.  With
+ *       EC = e^{w_im t} cos(k z - w_re t),    ES = e^{w_im t} sin(k z - w_re t)
+ *     every variable of section 7 with angular factor Theta(theta) has the value A_re (Theta EC) - A_im (Theta ES) -- the real
+ *     part of A Theta e^{i (k z - w t)} --, xi_x, xi_y, v_x, v_y are the section-7 rotations of those; fp64 throughout, rounded
+ *     once.  At w_im = 0 and A_im = 0 this is section 7's expression, grouping included: the same bits.  d_points, var_mask,
+ *     v_scale, ES_FIELD_Z_REFERENCE_ANGLE, ES_FIELD_BIG_ENDIAN, the size limits, the alignment rule (16-byte stores where the
+ *     row is 16-byte aligned, 4-byte stores otherwise, the same bits either way), the empty-size and mask rules are those of
+ *     section 7.
+ *     Not offered: the twisted cylinder at complex frequency; Cartesian sampling and vorticity (section 8) of unstable
+ *     cylinder modes; physically phased amplitudes (the i between the radial and the other components).
+ * ====================================================================================================== */
+int es_cyl_complex_eigenfunction(es_context* ctx, const es_problem* prob,
+                                 const double* d_k, const double* d_w_re, const double* d_w_im, int n,
+                                 double* d_int_value, double* d_int_flux,      /* n x N complex      */
+                                 int n_ext, double* d_ext_x,                   /* n x n_ext real     */
+                                 double* d_ext_value, double* d_ext_flux,      /* n x n_ext complex  */
+                                 uint8_t* d_status /* n, may be NULL */);
+
+int es_cyl_complex_polarisation(es_context* ctx, const double* d_k, const double* d_w_re, const double* d_w_im, int n,
+                                int n_nodes, const double* d_int_value, const double* d_int_flux,   /* n x N complex     */
+                                int n_ext, const double* d_ext_x,                                    /* n x n_ext real    */
+                                const double* d_ext_value, const double* d_ext_flux,                 /* n x n_ext complex */
+                                const es_field_profiles* profiles, int m, double rho_e, double vA_e, double c_e, double cT_e,
+                                int flags, double* d_radius /* n x n_r */, double* d_amp /* n x 7 x n_r complex */);
+
+int es_cyl_complex_field_synthesis(es_context* ctx, const double* d_radius, const double* d_amp /* 7 x n_r complex */,
+                                   int n_r, int m, double k, double w_re, double w_im,
+                                   const double* d_theta, int n_theta, const double* d_z, int n_z, const double* d_t, int n_t,
+                                   uint32_t var_mask, double v_scale, int flags,
+                                   float* d_points /* may be NULL */, float* d_out);
 
 #ifdef __cplusplus
 }
