@@ -9,3 +9,4 @@ from .cyl_uniform import CylinderUniform  # noqa: F401
 from . import postprocess  # noqa: F401
 from .complex_flow import SlabComplexFlow, SlabFlowKH  # noqa: F401
 from .cyl_complex import CylinderComplex  # noqa: F401
+from .cylt_complex import RotatingCylinderComplex  # noqa: F401

@@ -340,4 +340,9 @@ def _sig(lib):
                                                     d, d, d, d, i, vp, vp]
         lib.es_cyl_complex_field_synthesis.argtypes = [vp, vp, vp, i, i, d, d, d, vp, i, vp, i, vp, i, C.c_uint32, d, i, vp,
                                                        vp]
+    # (17) complex frequencies on the twisted cylinder: the signatures of (14)
+    if hasattr(lib, "es_cylt_complex_eval_grid"):           # likewise
+        lib.es_cylt_complex_eval_grid.argtypes = lib.es_cyl_complex_eval_grid.argtypes
+        lib.es_cylt_complex_eval_points.argtypes = lib.es_cyl_complex_eval_points.argtypes
+        lib.es_cylt_complex_find_roots.argtypes = lib.es_cyl_complex_find_roots.argtypes
     return lib

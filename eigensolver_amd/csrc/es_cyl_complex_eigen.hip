@@ -29,6 +29,7 @@ __global__ __launch_bounds__(64) void cyleig_interior_kernel(ShootDev P, const d
                                                              double* __restrict__ value, double* __restrict__ flux,
                                                              uint8_t* __restrict__ stout) {
   constexpr bool DIAG = FamTraits<FAM>::DIAG;
+  constexpr int NB = FamTraits<FAM>::NB, NE = FamTraits<FAM>::NE;
   __shared__ double sb[CYLC_LDS_DOUBLES];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;

@@ -1,14 +1,15 @@
-// The complex-frequency evaluation of the untwisted cylinder (FAM_CYL0), written once over the scalar Z
-// (include/eigensolver_amd.h sections 14 and 15; the CPU restatements are tests/cyl_complex_model.py and
-// tests/cyl_complex_slope_model.py):
-//   Z = esb::cz        the plain complex value: es_cyl_complex.hip (determinant, roots)
+// The complex-frequency evaluation of the cylinder, written once over the scalar Z and the family F
+// (include/eigensolver_amd.h sections 14, 15 and 17; the CPU restatements are tests/cyl_complex_model.py,
+// tests/cyl_complex_slope_model.py and tests/cylt_complex_model.py):
+//   Z = esb::cz        the plain complex value: es_cyl_complex.hip (determinant, roots), es_cylt_complex.hip (the same for the
+//                      twisted family, F = FAM_CYLT)
 //   Z = esb::CJet<1>   value and d/d omega: the Newton steps of es_cyl_complex_slopes.hip
 //   Z = esb::CJet<2>   value, d/d omega and d/dk: the slopes
 // The wavenumber comes as K: a plain double where it is a constant of the differentiation (cz, CJet<1>), the jet (k, 0, 1)
-// for CJet<2>.
+// for CJet<2>.  F defaults to FAM_CYL0, the untwisted cylinder: the translation units of sections 14 - 16 name no family.
 //
-// Interior: the FAM_CYL0 formula text of es_shoot_device.hpp (make_entry, coef_pre, coef_finish, adjoint_start,
-// rk4_step_adjoint<0>, boundary_algebra) instantiated with Z, TRACK = false, the plain (not scaled, normalised) RK4 step, one
+// Interior: the formula text of es_shoot_device.hpp for the family (make_entry, coef_pre, coef_finish, adjoint_start,
+// rk4_step_adjoint<SHAPE>, boundary_algebra) instantiated with Z, TRACK = false, the plain (not scaled, normalised) RK4 step, one
 // IEEE complex division per node.  Nothing of the coefficient formulas is restated here.
 // Exterior, written for the complex case (cyl_exterior): m_e and xi_e_const as exterior_cylinder, mu = principal sqrt(m_e),
 // K_n and I_n at complex argument (es_bessel_complex.hpp), the same far-field initial values and I-admixture.  The solution is
@@ -29,10 +30,10 @@
 namespace es_cyl_complex_shared {
 using namespace es_complex_shared;
 using esb::cz;
-constexpr int FAM = FAM_CYL0;
-constexpr int NB = FamTraits<FAM>::NB;
-constexpr int NE = FamTraits<FAM>::NE;
-constexpr int CYLC_LDS_DOUBLES = NB * (2 * CH + 1);         // one chunk: nodes and mid-points of CH steps
+constexpr int FAM = FAM_CYL0;                               // the family of sections 14 - 16
+// No NB / NE at this level: every function takes the sizes of its own family from FamTraits<F>.
+template <int F> constexpr int cyl_lds_doubles() { return FamTraits<F>::NB * (2 * CH + 1); }   // one chunk: nodes and mid-points of CH steps
+constexpr int CYLC_LDS_DOUBLES = cyl_lds_doubles<FAM>();
 
 // what boundary_algebra reads of an exterior
 template <class Z> struct CylcExterior {
@@ -117,26 +118,39 @@ template <class Z, class K> __device__ __forceinline__ CylcExterior<Z> cyl_exter
 
 // Copies the base table of the nst steps from step c0 on (2 nst + 1 points, point-major) into the LDS buffer `sb`, between two
 // barriers: every lane of the workgroup makes every call.
+// The twisted family's 20 fields are walked with one running row pointer: unrolled, their 19 row offsets are formed once per
+// kernel and held in scalar registers through every inlined copy of the evaluation (the refinement kernel has four), 38 of
+// the 61 scalar registers that kernel then spilled to vector lanes.  Same copies either way.
+template <int F = FAM>
 __device__ __forceinline__ void cyl_stage_chunk(const ShootDev& P, int c0, int nst, double* __restrict__ sb) {
+  constexpr int NB = FamTraits<F>::NB;
   __syncthreads();
+  if constexpr (NB > 8) {
+    const double* __restrict__ row = P.base + 2 * c0;
+#pragma nounroll
+    for (int f = 0; f < NB; ++f, row += P.npts)
+      for (int i = threadIdx.x; i < 2 * nst + 1; i += blockDim.x) sb[i * NB + f] = row[i];
+  } else {
 #pragma unroll
-  for (int f = 0; f < NB; ++f)
-    for (int i = threadIdx.x; i < 2 * nst + 1; i += blockDim.x) sb[i * NB + f] = P.base[(size_t)f * P.npts + 2 * c0 + i];
+    for (int f = 0; f < NB; ++f)
+      for (int i = threadIdx.x; i < 2 * nst + 1; i += blockDim.x) sb[i * NB + f] = P.base[(size_t)f * P.npts + 2 * c0 + i];
+  }
   __syncthreads();
 }
 
 // coefficients of the node whose base fields are at b
-template <class Z>
+template <class Z, int F = FAM>
 __device__ __forceinline__ CoefT<Z> cyl_node(const ShootDev& P, const KScalT<Z>& s, const Z& w, const double* __restrict__ bn, Z* e) {
+  constexpr int NB = FamTraits<F>::NB, NE = FamTraits<F>::NE;
   double b[NB], c[NE];
 #pragma unroll
   for (int f = 0; f < NB; ++f) b[f] = bn[f];
-  make_entry<FAM, false>(b, s, e, c);
+  make_entry<F, false>(b, s, e, c);
   SignTrack trk;
   CoefPreT<Z> C;
-  coef_pre<FAM, false>(e, c, P, s, w, C, trk);
+  coef_pre<F, false>(e, c, P, s, w, C, trk);
   CoefT<Z> A;
-  coef_finish<FAM>(C, 1.0 / C.den, A);
+  coef_finish<F>(C, 1.0 / C.den, A);
   return A;
 }
 
@@ -149,8 +163,9 @@ template <class Z> struct CylcMatch {
 };
 
 // P carries bc_const at its true scale (the launches pass bc_const_raw).  Every lane of the workgroup must call this.
-template <class Z, class K>
+template <class Z, class K, int F = FAM>
 __device__ __forceinline__ CylcMatch<Z> cyl_shoot_point(const ShootDev& P, const K& k, const Z& w, double* __restrict__ sb) {
+  constexpr int NB = FamTraits<F>::NB, NE = FamTraits<F>::NE;
   const KScalT<Z> s = make_kscal(P, Z(k));
   const CylcExterior<Z> X = cyl_exterior<Z, K>(P, k, w);
   const int nsteps = P.n_nodes - 1;
@@ -162,20 +177,20 @@ __device__ __forceinline__ CylcMatch<Z> cyl_shoot_point(const ShootDev& P, const
   for (int c = nchunks - 1; c >= 0; --c) {
     const int c0 = c * CH;
     const int nst = (nsteps - c0 < CH) ? (nsteps - c0) : CH;
-    cyl_stage_chunk(P, c0, nst, sb);
+    cyl_stage_chunk<F>(P, c0, nst, sb);
     if (c == nchunks - 1) {                            // last node: start vector of the march
-      B0 = cyl_node(P, s, w, sb + 2 * nst * NB, e);
-      adjoint_start<FAM>(P, B0, zp, zq);
+      B0 = cyl_node<Z, F>(P, s, w, sb + 2 * nst * NB, e);
+      adjoint_start<F>(P, B0, zp, zq);
     }
     for (int j = nst - 1; j >= 0; --j) {
-      const CoefT<Z> Bm = cyl_node(P, s, w, sb + (2 * j + 1) * NB, e);
-      const CoefT<Z> B1 = cyl_node(P, s, w, sb + (2 * j) * NB, e);
-      rk4_step_adjoint<FamTraits<FAM>::SHAPE>(zp, zq, B0, Bm, B1, h, h2, h6, h3);
+      const CoefT<Z> Bm = cyl_node<Z, F>(P, s, w, sb + (2 * j + 1) * NB, e);
+      const CoefT<Z> B1 = cyl_node<Z, F>(P, s, w, sb + (2 * j) * NB, e);
+      rk4_step_adjoint<FamTraits<F>::SHAPE>(zp, zq, B0, Bm, B1, h, h2, h6, h3);
       B0 = B1;
     }
   }
   // e: the entries of the boundary node (read by the slab branches of boundary_algebra only)
-  const MismatchT<Z> M = boundary_algebra<FAM>(P, s, w, X, zp, zq, e);
+  const MismatchT<Z> M = boundary_algebra<F>(P, s, w, X, zp, zq, e);
   CylcMatch<Z> R;
   R.outer = M.outer;
   R.inner = M.inner;

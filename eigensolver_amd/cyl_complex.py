@@ -19,20 +19,20 @@ from .complex_flow import ComplexTracing, _distinct
 from .shooting import ShootProblem, W_ABSOLUTE, W_PHASE_SPEED, _frame_chunks, _frames_out, var_mask  # noqa: F401
 
 
-class CylinderComplex(ComplexTracing):
-    """D_c(k, omega) of one cylinder equilibrium at complex omega: grids, point lists, roots, and through ComplexTracing
-    the slopes and the Newton tracing of section 15 -- root_slopes(mode, k, w, count=None, m=None), group_velocity(mode,
-    roots, count=None, m=None), newton(mode, k, w0, ..., m=None) and densify(mode, k, w, k_fine, shift_factor=4.0, m=None,
-    **newton_kw), with the return conventions of SlabComplexFlow.  One ShootProblem per (mode, m), created on first use."""
-    _SELECT = ("m",)
+class CylinderEvaluation:
+    """The evaluation and root-search plumbing of sections 14 and 17, written once over the three entry points
+    <_PREFIX>eval_grid, <_PREFIX>eval_points and <_PREFIX>find_roots (same signatures): CylinderComplex and
+    cylt_complex.RotatingCylinderComplex.  One ShootProblem per (mode, m), created on first use."""
+    _PREFIX = None                                  # "es_cyl_complex_" / "es_cylt_complex_"
     P_TOL = 4.0                                     # acceptance of a refined root, percent: that of SlabComplexFlow
 
-    def __init__(self, equilibrium, ctx=None):
-        if getattr(equilibrium, "twisted", True):
-            raise TypeError("CylinderComplex takes an untwisted cylinder equilibrium (CylinderDensity, CylinderFlow)")
+    def _init(self, equilibrium, ctx):
         self.eq = equilibrium
         self.ctx = ctx or _lib.Context()
         self._problems = {}
+
+    def _entry(self, name):
+        return getattr(self.ctx.lib, self._PREFIX + name)
 
     def problem(self, mode, m=None):
         key = (mode, (1 if mode == "kink" else 0) if m is None else int(m))
@@ -45,13 +45,6 @@ class CylinderComplex(ComplexTracing):
             p.close()
         self._problems = {}
 
-    # ---- slopes and Newton tracing (C ABI section 15): ComplexTracing over these two calls ----------------------------------
-    def _slopes_call(self, p, *args):
-        return self.ctx.lib.es_cyl_complex_root_slopes(self.ctx.handle, p.handle, *args)
-
-    def _newton_call(self, p, *args):
-        return self.ctx.lib.es_cyl_complex_newton(self.ctx.handle, p.handle, *args)
-
     # ---- evaluation ------------------------------------------------------------------------------------------------
     def eval_grid(self, mode, k, w_re, w_im, w_mode=W_ABSOLUTE, m=None):
         """D_c[nk, n_im, n_re] (complex128 tensor), status[nk, n_im, n_re], rel[nk, n_im, n_re]."""
@@ -63,9 +56,8 @@ class CylinderComplex(ComplexTracing):
         Dim = torch.empty_like(Dre)
         rel = torch.empty_like(Dre)
         st = torch.empty((nk, nim, nre), dtype=torch.uint8, device=dk.device)
-        rc = self.ctx.lib.es_cyl_complex_eval_grid(self.ctx.handle, p.handle, _lib.ptr(dk), nk, _lib.ptr(dre), nre,
-                                                   _lib.ptr(dim), nim, int(w_mode), _lib.ptr(Dre), _lib.ptr(Dim),
-                                                   _lib.ptr(rel), _lib.ptr(st))
+        rc = self._entry("eval_grid")(self.ctx.handle, p.handle, _lib.ptr(dk), nk, _lib.ptr(dre), nre, _lib.ptr(dim), nim,
+                                      int(w_mode), _lib.ptr(Dre), _lib.ptr(Dim), _lib.ptr(rel), _lib.ptr(st))
         _lib.check(self.ctx.handle, rc)
         return torch.complex(Dre, Dim), st, rel
 
@@ -83,9 +75,9 @@ class CylinderComplex(ComplexTracing):
         st = torch.empty(n, dtype=torch.uint8, device=dk.device)
         outer = torch.empty(n, dtype=torch.complex128, device=dk.device) if parts else None
         inner = torch.empty(n, dtype=torch.complex128, device=dk.device) if parts else None
-        rc = self.ctx.lib.es_cyl_complex_eval_points(self.ctx.handle, p.handle, _lib.ptr(dk), _lib.ptr(dre), _lib.ptr(dim), n,
-                                                     _lib.ptr(Dre), _lib.ptr(Dim), _lib.ptr(rel), _lib.ptr(st),
-                                                     _lib.ptr(outer) if parts else None, _lib.ptr(inner) if parts else None)
+        rc = self._entry("eval_points")(self.ctx.handle, p.handle, _lib.ptr(dk), _lib.ptr(dre), _lib.ptr(dim), n,
+                                        _lib.ptr(Dre), _lib.ptr(Dim), _lib.ptr(rel), _lib.ptr(st),
+                                        _lib.ptr(outer) if parts else None, _lib.ptr(inner) if parts else None)
         _lib.check(self.ctx.handle, rc)
         D = torch.complex(Dre, Dim)
         return (D, st, rel, outer, inner) if parts else (D, st, rel)
@@ -108,9 +100,9 @@ class CylinderComplex(ComplexTracing):
             rt = _lib.ComplexRootTable(_lib.ptr(t["k"]), _lib.ptr(t["w_re"]), _lib.ptr(t["w_im"]), _lib.ptr(t["resid"]),
                                        _lib.ptr(t["row"]), _lib.ptr(t["flag"]), cap)
             n = C.c_int(0)
-            rc = self.ctx.lib.es_cyl_complex_find_roots(self.ctx.handle, p.handle, _lib.ptr(dk), nk, _lib.ptr(dre), nre,
-                                                        _lib.ptr(dim), nim, int(w_mode), _lib.ptr(Dre), _lib.ptr(Dim),
-                                                        _lib.ptr(status), int(n_iter), tol, C.byref(rt), C.byref(n))
+            rc = self._entry("find_roots")(self.ctx.handle, p.handle, _lib.ptr(dk), nk, _lib.ptr(dre), nre, _lib.ptr(dim), nim,
+                                           int(w_mode), _lib.ptr(Dre), _lib.ptr(Dim), _lib.ptr(status), int(n_iter), tol,
+                                           C.byref(rt), C.byref(n))
             _lib.check(self.ctx.handle, rc, allow_capacity=True)
             if rc == 3 and capacity is None:
                 cap = n.value
@@ -129,6 +121,27 @@ class CylinderComplex(ComplexTracing):
         ok = roots["flag"].cpu().numpy() == 1
         w, row = roots["w"].cpu().numpy()[ok], roots["row"].cpu().numpy()[ok]
         return [_distinct(w[row == r]) for r in range(len(k))]
+
+
+class CylinderComplex(CylinderEvaluation, ComplexTracing):
+    """D_c(k, omega) of one cylinder equilibrium at complex omega: grids, point lists, roots (CylinderEvaluation), and through
+    ComplexTracing the slopes and the Newton tracing of section 15 -- root_slopes(mode, k, w, count=None, m=None),
+    group_velocity(mode, roots, count=None, m=None), newton(mode, k, w0, ..., m=None) and densify(mode, k, w, k_fine,
+    shift_factor=4.0, m=None, **newton_kw), with the return conventions of SlabComplexFlow."""
+    _SELECT = ("m",)
+    _PREFIX = "es_cyl_complex_"
+
+    def __init__(self, equilibrium, ctx=None):
+        if getattr(equilibrium, "twisted", True):
+            raise TypeError("CylinderComplex takes an untwisted cylinder equilibrium (CylinderDensity, CylinderFlow)")
+        self._init(equilibrium, ctx)
+
+    # ---- slopes and Newton tracing (C ABI section 15): ComplexTracing over these two calls ----------------------------------
+    def _slopes_call(self, p, *args):
+        return self.ctx.lib.es_cyl_complex_root_slopes(self.ctx.handle, p.handle, *args)
+
+    def _newton_call(self, p, *args):
+        return self.ctx.lib.es_cyl_complex_newton(self.ctx.handle, p.handle, *args)
 
     # ---- eigenfunctions and perturbation fields (C ABI section 16) -----------------------------------------------------
     def eigenfunction(self, mode, k, w, n_ext=500, m=None):

@@ -982,7 +982,8 @@ int es_shoot_newton(es_context* ctx, const es_problem* prob, const double* d_k, 
  *     root search -- the unstable (Kelvin-Helmholtz) modes of a cylinder whose axial jet is fast enough, where the root leaves
  *     the real axis and sections 2 and 13 find nothing.  ES_GEOM_CYLINDER problems only (non-uniform density or axial flow,
  *     any m, both axis conditions, both signs of r); every other geometry gets ES_ERR_UNSUPPORTED (the flow slab has
- *     section 6, whose calls in turn keep refusing cylinders).  Values only.
+ *     section 6, whose calls in turn keep refusing cylinders; the twisted cylinder has section 17).  Values only (DESIGN.md
+ *     section 8i).
  *     What is computed: the interior of section 2 -- the same node grid, the same coefficient formulas, one classical RK4
  *     step per interval, the adjoint row march, the axis condition by superposition -- in complex arithmetic, and the
  *     exterior P_e = a I_m(mu |r|) + b K_m(mu |r|) with mu = principal sqrt(m_e), K and I at complex argument, the
@@ -1024,7 +1025,7 @@ int es_cyl_complex_find_roots(es_context* ctx, const es_problem* prob, const dou
  *       -D_c / D_w              :  the Newton correction, quadratic because D_c is holomorphic (section 14 takes 12 secant
  *                                   steps from a cell centre, plus the grid row that found the cell).
  *     Both calls take the problem as section 14 does: ES_GEOM_CYLINDER only, every other geometry -- the twisted cylinder,
- *     which is still not offered at complex frequency, and the slabs -- gets ES_ERR_UNSUPPORTED.  Both are asynchronous on the
+ *     whose complex-frequency determinant and roots are section 17, and the slabs -- gets ES_ERR_UNSUPPORTED.  Both are asynchronous on the
  *     context's stream with no host read-back; n == 0 succeeds and touches nothing (the arrays may then be NULL).  d_count
  *     (may be NULL): as in sections 10 - 13 -- the kernels use min(max(*d_count, 0), n) and leave entries beyond it alone.
  *
@@ -1051,7 +1052,8 @@ int es_cyl_complex_find_roots(es_context* ctx, const es_problem* prob, const dou
  *       done about it.  On the real axis d omega / dk is real: the group speed of section 11.
  *     ES_ERR_INVALID_ARG: n < 0, max_iter < 0, step_cap, max_shift or tol_percent not positive, a null problem, any array
  *     but d_count and d_dwdk null with n > 0.
- *     Not offered: the twisted cylinder, second derivatives.  (Eigenfunctions and fields at complex roots: section 16.)
+ *     Not offered: slopes and Newton tracing on the twisted cylinder (its values and roots: section 17), second derivatives.
+ *     (Eigenfunctions and fields at complex roots: section 16.)
  * ====================================================================================================== */
 int es_cyl_complex_root_slopes(es_context* ctx, const es_problem* prob,
                                const double* d_k, const double* d_w_re, const double* d_w_im, int n,
@@ -1114,7 +1116,8 @@ int es_cyl_complex_newton(es_context* ctx, const es_problem* prob,
  *     v_scale, ES_FIELD_Z_REFERENCE_ANGLE, ES_FIELD_BIG_ENDIAN, the size limits, the alignment rule (16-byte stores where the
  *     row is 16-byte aligned, 4-byte stores otherwise, the same bits either way), the empty-size and mask rules are those of
  *     section 7.
- *     Not offered: the twisted cylinder at complex frequency; Cartesian sampling and vorticity (section 8) of unstable
+ *     Not offered: eigenfunctions and fields of the twisted cylinder at complex frequency (its determinant and roots:
+ *     section 17); Cartesian sampling and vorticity (section 8) of unstable
  *     cylinder modes; physically phased amplitudes (the i between the radial and the other components).
  * ====================================================================================================== */
 int es_cyl_complex_eigenfunction(es_context* ctx, const es_problem* prob,
@@ -1136,6 +1139,38 @@ int es_cyl_complex_field_synthesis(es_context* ctx, const double* d_radius, cons
                                    const double* d_theta, int n_theta, const double* d_z, int n_z, const double* d_t, int n_t,
                                    uint32_t var_mask, double v_scale, int flags,
                                    float* d_points /* may be NULL */, float* d_out);
+
+/* ======================================================================================================
+ * (17) Complex frequencies on the twisted (rotating) cylinder: section 14 for ES_GEOM_CYLINDER_TWIST problems -- the
+ *     determinant at omega = omega_r + i omega_i and its root search, the unstable (Kelvin-Helmholtz) modes of a tube with
+ *     azimuthal shear.  ES_GEOM_CYLINDER_TWIST problems only (m >= 0 as in section 2, the three axis conditions, both values
+ *     of c1_power, both signs of r); every other geometry gets ES_ERR_UNSUPPORTED with the outputs untouched (the untwisted
+ *     cylinder has section 14, whose calls in turn keep refusing twisted problems).  Values only.
+ *     What is computed: the interior of section 2 for this family -- the 20-field base table, the general coefficient set
+ *     with v_phi and B_phi, one classical RK4 step of the full 2x2 system per interval, the adjoint row march, the axis
+ *     condition by superposition (ES_AXIS_ROTATION_KINK: P(r_ax) + bc_const xi_e = 0) -- in complex arithmetic, and the
+ *     exterior of section 14 as it is: the medium outside is the same.  Normalisation P_e(boundary) = 1, so at omega_i = 0
+ *         D_c = sign(P_e(boundary)) D of es_shoot_eval_points,    Im D_c = 0,
+ *     and D_c(k, conj omega) = conj D_c(k, omega).  outer, inner, rel, the statuses (ES_PT_LEAKY where Re(m_e) < 0,
+ *     ES_PT_NONFINITE where m_e, xi_e_const or the result is not finite, never ES_PT_CONTINUUM; NaN outputs unless ES_PT_OK),
+ *     the signatures, the grid layout, w_mode, the cell rule, the secant refinement, the flag, the order of the table, the
+ *     capacity convention and the argument checks are those of section 14, word for word.  A call with no points succeeds
+ *     and touches nothing.  The eval calls are asynchronous on the context's stream; es_cylt_complex_find_roots synchronises.
+ *     Not offered: slopes, Newton tracing (section 15), eigenfunctions and fields (section 16) of twisted problems; m < 0.
+ * ====================================================================================================== */
+int es_cylt_complex_eval_grid(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
+                              const double* d_w_re, int n_re, const double* d_w_im, int n_im, int w_mode,
+                              double* d_D_re, double* d_D_im, double* d_rel /* may be NULL */, uint8_t* d_status);
+
+int es_cylt_complex_eval_points(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w_re,
+                                const double* d_w_im, int n, double* d_D_re, double* d_D_im,
+                                double* d_rel /* may be NULL */, uint8_t* d_status,
+                                double* d_outer /* [n][2], may be NULL */, double* d_inner /* [n][2], may be NULL */);
+
+int es_cylt_complex_find_roots(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
+                               const double* d_w_re, int n_re, const double* d_w_im, int n_im, int w_mode,
+                               const double* d_D_re, const double* d_D_im, const uint8_t* d_status, int n_iter,
+                               double tol_percent, es_complex_root_table* table, int* out_count);
 
 #ifdef __cplusplus
 }
