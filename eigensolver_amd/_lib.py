@@ -345,4 +345,8 @@ def _sig(lib):
         lib.es_cylt_complex_eval_grid.argtypes = lib.es_cyl_complex_eval_grid.argtypes
         lib.es_cylt_complex_eval_points.argtypes = lib.es_cyl_complex_eval_points.argtypes
         lib.es_cylt_complex_find_roots.argtypes = lib.es_cyl_complex_find_roots.argtypes
+    # (18) slopes and Newton tracing of complex roots of the twisted cylinder: the signatures of (15)
+    if hasattr(lib, "es_cylt_complex_root_slopes"):         # likewise
+        lib.es_cylt_complex_root_slopes.argtypes = lib.es_cyl_complex_root_slopes.argtypes
+        lib.es_cylt_complex_newton.argtypes = lib.es_cyl_complex_newton.argtypes
     return lib

@@ -81,8 +81,8 @@ def _distinct(w, tol=1e-8):
 
 
 class ComplexTracing:
-    """Slopes and Newton tracing of complex roots, written once for the geometries that have the two C calls (sections 12 and
-    15 of include/eigensolver_amd.h): root_slopes, group_velocity, newton and densify.  A class that mixes this in has ctx,
+    """Slopes and Newton tracing of complex roots, written once for the geometries that have the two C calls (sections 12, 15
+    and 18 of include/eigensolver_amd.h): root_slopes, group_velocity, newton and densify.  A class that mixes this in has ctx,
     P_TOL, problem(mode, **select) and the two calls, _slopes_call(problem, *args) and _newton_call(problem, *args), args
     being the C arguments after the problem (and, for the slab, the variant).  `select` stands for the keywords that pick the
     problem beside the mode (_SELECT: none for the slab, m for the cylinder)."""

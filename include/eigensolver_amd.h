@@ -1025,7 +1025,7 @@ int es_cyl_complex_find_roots(es_context* ctx, const es_problem* prob, const dou
  *       -D_c / D_w              :  the Newton correction, quadratic because D_c is holomorphic (section 14 takes 12 secant
  *                                   steps from a cell centre, plus the grid row that found the cell).
  *     Both calls take the problem as section 14 does: ES_GEOM_CYLINDER only, every other geometry -- the twisted cylinder,
- *     whose complex-frequency determinant and roots are section 17, and the slabs -- gets ES_ERR_UNSUPPORTED.  Both are asynchronous on the
+ *     which has sections 17 and 18 for this, and the slabs -- gets ES_ERR_UNSUPPORTED.  Both are asynchronous on the
  *     context's stream with no host read-back; n == 0 succeeds and touches nothing (the arrays may then be NULL).  d_count
  *     (may be NULL): as in sections 10 - 13 -- the kernels use min(max(*d_count, 0), n) and leave entries beyond it alone.
  *
@@ -1052,7 +1052,7 @@ int es_cyl_complex_find_roots(es_context* ctx, const es_problem* prob, const dou
  *       done about it.  On the real axis d omega / dk is real: the group speed of section 11.
  *     ES_ERR_INVALID_ARG: n < 0, max_iter < 0, step_cap, max_shift or tol_percent not positive, a null problem, any array
  *     but d_count and d_dwdk null with n > 0.
- *     Not offered: slopes and Newton tracing on the twisted cylinder (its values and roots: section 17), second derivatives.
+ *     Not offered: second derivatives.  (Slopes and Newton tracing on the twisted cylinder: section 18.)
  *     (Eigenfunctions and fields at complex roots: section 16.)
  * ====================================================================================================== */
 int es_cyl_complex_root_slopes(es_context* ctx, const es_problem* prob,
@@ -1156,7 +1156,7 @@ int es_cyl_complex_field_synthesis(es_context* ctx, const double* d_radius, cons
  *     the signatures, the grid layout, w_mode, the cell rule, the secant refinement, the flag, the order of the table, the
  *     capacity convention and the argument checks are those of section 14, word for word.  A call with no points succeeds
  *     and touches nothing.  The eval calls are asynchronous on the context's stream; es_cylt_complex_find_roots synchronises.
- *     Not offered: slopes, Newton tracing (section 15), eigenfunctions and fields (section 16) of twisted problems; m < 0.
+ *     Not offered: eigenfunctions and fields (section 16) of twisted problems; m < 0.  (Slopes and Newton tracing: section 18.)
  * ====================================================================================================== */
 int es_cylt_complex_eval_grid(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
                               const double* d_w_re, int n_re, const double* d_w_im, int n_im, int w_mode,
@@ -1171,6 +1171,34 @@ int es_cylt_complex_find_roots(es_context* ctx, const es_problem* prob, const do
                                const double* d_w_re, int n_re, const double* d_w_im, int n_im, int w_mode,
                                const double* d_D_re, const double* d_D_im, const uint8_t* d_status, int n_iter,
                                double tol_percent, es_complex_root_table* table, int* out_count);
+
+/* ======================================================================================================
+ * (18) Slopes and Newton tracing of complex roots of the twisted (rotating) cylinder (the unstable modes of section 17):
+ *     section 15 for ES_GEOM_CYLINDER_TWIST problems.  ES_GEOM_CYLINDER_TWIST problems only (m >= 0, the three axis
+ *     conditions, both values of c1_power, both signs of r); every other geometry gets ES_ERR_UNSUPPORTED with the outputs
+ *     untouched (the untwisted cylinder has section 15, whose calls in turn keep refusing twisted problems).
+ *     What is computed: the program text of section 17 -- the 20-field base table, the general coefficient set with v_phi and
+ *     B_phi, the full-shape RK4 step, the adjoint row march, the axis condition, the Bessel exterior -- carried in jets of
+ *     three complex components (value, d/d omega, d/dk) for the slopes and of two (value, d/d omega) for the Newton steps.
+ *     Row 0 of d_outer / d_inner is the outer and inner of es_cylt_complex_eval_points.  On the real axis d omega / dk is
+ *     real, the group speed of section 11, and the jets at conj omega are the conjugates of those at omega.
+ *     The signatures, the output layouts ([3][n][2] outer / inner; w, resid, dwdk, iters, flag), d_count, the statuses, the
+ *     NaN rule, the Newton rule (that of es_complex_newton, step for step), the flag, the argument checks and the
+ *     asynchrony are those of section 15, word for word.
+ *     Not offered: eigenfunctions and fields at complex roots of twisted problems; m < 0; second derivatives.
+ * ====================================================================================================== */
+int es_cylt_complex_root_slopes(es_context* ctx, const es_problem* prob,
+                                const double* d_k, const double* d_w_re, const double* d_w_im, int n,
+                                const int32_t* d_count /* may be NULL */,
+                                double* d_outer /* [3][n][2]: value, d/dw, d/dk; (re, im) pairs */,
+                                double* d_inner /* [3][n][2] */, uint8_t* d_status);
+
+int es_cylt_complex_newton(es_context* ctx, const es_problem* prob,
+                           const double* d_k, const double* d_guess_re, const double* d_guess_im, int n,
+                           const int32_t* d_count /* may be NULL */,
+                           int max_iter, double step_cap, double max_shift, double tol_percent,
+                           double* d_w_re, double* d_w_im, double* d_resid,
+                           double* d_dwdk /* [n][2], may be NULL */, int32_t* d_iters, int32_t* d_flag);
 
 #ifdef __cplusplus
 }
