@@ -1,9 +1,9 @@
 // The root search of the complex-frequency determinants, written once for both geometries (include/eigensolver_amd.h sections
-// 6 and 14): the candidate cells (winding-number flags, ordered compaction, cell centres: the kernels live in es_complex.hip),
+// 6, 14 and 17): the candidate cells (winding-number flags, ordered compaction, cell centres: the kernels live in es_complex.hip),
 // the complex secant refinement over an evaluator, and the host side of a find_roots call.  The flow slab (es_complex.hip)
-// and the cylinder (es_cyl_complex.hip) differ in the evaluator of the refinement kernel and in their argument check only.
-// Beside it the Newton rule of sections 12 and 15 (cx_newton_lane), over an evaluator in the same way: es_complex_slopes.hip
-// and es_cyl_complex_slopes.hip.
+// and the cylinder (es_cyl_complex.hip, both families) differ in the evaluator of the refinement kernel and in their argument
+// check only.  Beside it the Newton rule of sections 12, 15 and 18 (cx_newton_lane), over an evaluator in the same way:
+// es_complex_slopes.hip and es_cyl_complex_slopes.hip.
 #pragma once
 #include "es_complex_shared.hpp"
 
@@ -63,10 +63,10 @@ struct CxNewtonPoint {
   uint8_t st;
 };
 
-// Newton in omega at fixed k for guess i of the workgroup's cnt (es_complex_newton, es_cyl_complex_newton).  step(k, w) is
-// the evaluation with d/d omega, last(k, w) the one with d/dk as well; both have barriers, so every lane of the workgroup
-// makes this call.  A lane that has stopped keeps evaluating at its frozen omega; the workgroup leaves the loop together once
-// no lane is active.  Lanes past cnt iterate on dummy inputs and store nothing.
+// Newton in omega at fixed k for guess i of the workgroup's cnt (es_complex_newton, es_cyl_complex_newton,
+// es_cylt_complex_newton).  step(k, w) is the evaluation with d/d omega, last(k, w) the one with d/dk as well; both have
+// barriers, so every lane of the workgroup makes this call.  A lane that has stopped keeps evaluating at its frozen omega;
+// the workgroup leaves the loop together once no lane is active.  Lanes past cnt iterate on dummy inputs and store nothing.
 template <class Step, class Final>
 __device__ __forceinline__ void cx_newton_lane(Step step, Final last, const double* __restrict__ kv,
                                                const double* __restrict__ gre, const double* __restrict__ gim, int i, int cnt,

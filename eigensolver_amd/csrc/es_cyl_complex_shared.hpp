@@ -1,12 +1,11 @@
 // The complex-frequency evaluation of the cylinder, written once over the scalar Z and the family F
-// (include/eigensolver_amd.h sections 14, 15 and 17; the CPU restatements are tests/cyl_complex_model.py,
-// tests/cyl_complex_slope_model.py and tests/cylt_complex_model.py):
-//   Z = esb::cz        the plain complex value: es_cyl_complex.hip (determinant, roots), es_cylt_complex.hip (the same for the
-//                      twisted family, F = FAM_CYLT)
-//   Z = esb::CJet<1>   value and d/d omega: the Newton steps of es_cyl_complex_slopes.hip
+// (include/eigensolver_amd.h sections 14, 15, 17 and 18; the CPU restatements are tests/cyl_complex_model.py,
+// tests/cyl_complex_slope_model.py, tests/cylt_complex_model.py and tests/cylt_complex_slope_model.py):
+//   Z = esb::cz        the plain complex value: es_cyl_complex.hip (determinant, roots; both families)
+//   Z = esb::CJet<1>   value and d/d omega: the Newton steps of es_cyl_complex_slopes.hip (both families)
 //   Z = esb::CJet<2>   value, d/d omega and d/dk: the slopes
 // The wavenumber comes as K: a plain double where it is a constant of the differentiation (cz, CJet<1>), the jet (k, 0, 1)
-// for CJet<2>.  F defaults to FAM_CYL0, the untwisted cylinder: the translation units of sections 14 - 16 name no family.
+// for CJet<2>.  F defaults to FAM_CYL0, the untwisted cylinder: the translation units of section 16 name no family.
 //
 // Interior: the formula text of es_shoot_device.hpp for the family (make_entry, coef_pre, coef_finish, adjoint_start,
 // rk4_step_adjoint<SHAPE>, boundary_algebra) instantiated with Z, TRACK = false, the plain (not scaled, normalised) RK4 step, one
@@ -203,10 +202,13 @@ __device__ __forceinline__ CylcMatch<Z> cyl_shoot_point(const ShootDev& P, const
   return R;
 }
 
-inline int check_cyl_cx(es_context* ctx, const es_problem* prob) {
+// the family check of every entry point of sections 14 - 18
+template <int F = FAM> int check_cyl_cx(es_context* ctx, const es_problem* prob) {
   ES_REQUIRE(ctx, prob != nullptr, "null problem");
-  if (prob->dev.family != FAM_CYL0) {
-    ctx->last_error = "es_cyl_complex_* is implemented for ES_GEOM_CYLINDER problems only (the untwisted cylinder)";
+  if (prob->dev.family != F) {
+    ctx->last_error = F == FAM_CYLT
+                          ? "es_cylt_complex_* is implemented for ES_GEOM_CYLINDER_TWIST problems only (the twisted cylinder)"
+                          : "es_cyl_complex_* is implemented for ES_GEOM_CYLINDER problems only (the untwisted cylinder)";
     return ES_ERR_UNSUPPORTED;
   }
   return ES_SUCCESS;
@@ -217,6 +219,29 @@ inline ShootDev cyl_cx_dev(const es_problem* prob) {
   ShootDev P = prob->dev;
   P.bc_const = P.bc_const_raw;
   return P;
+}
+
+// The kernels that inline the evaluation more than once -- the refinement kernel of es_cyl_complex.hip (four copies) and the
+// Newton kernel of es_cyl_complex_slopes.hip (two) -- keep their wave-uniform arguments in vector registers for the families
+// named here: with the 20-field table of FAM_CYLT what the copies share would otherwise be spilled from scalar registers.
+// The comments at the two kernels say what is done and why; the evaluation and slopes kernels carry no remedy.
+template <int F> constexpr bool cyl_uniforms_in_vgprs = F == FAM_CYLT;
+#define ES_V(x) asm volatile("" : "+v"(x))
+__device__ __forceinline__ void vector_resident(ShootDev& P) {
+  ES_V(P.xb); ES_V(P.h); ES_V(P.rho_e); ES_V(P.vAe2); ES_V(P.ce2); ES_V(P.cTe2); ES_V(P.Se); ES_V(P.R_factor);
+  ES_V(P.ic0); ES_V(P.ic1); ES_V(P.bc_const); ES_V(P.base); ES_V(P.npts); ES_V(P.m); ES_V(P.m_ext); ES_V(P.axis_bc);
+  ES_V(P.c1_power); ES_V(P.accept_norm);
+}
+// The problem as one inlined copy of the evaluation takes it: for those families a copy with a scalar n_nodes of its own, from
+// which the copy derives its chunk and step counts; P itself otherwise.
+template <int F> __device__ __forceinline__ decltype(auto) cyl_own_counts(const ShootDev& P) {
+  if constexpr (cyl_uniforms_in_vgprs<F>) {
+    ShootDev Q = P;
+    asm volatile("" : "+s"(Q.n_nodes));
+    return Q;
+  } else {
+    return (P);
+  }
 }
 
 }  // namespace es_cyl_complex_shared

@@ -21,7 +21,8 @@ from .shooting import ShootProblem, W_ABSOLUTE, W_PHASE_SPEED, _frame_chunks, _f
 
 class CylinderEvaluation:
     """The evaluation and root-search plumbing of sections 14 and 17, written once over the three entry points
-    <_PREFIX>eval_grid, <_PREFIX>eval_points and <_PREFIX>find_roots (same signatures): CylinderComplex and
+    <_PREFIX>eval_grid, <_PREFIX>eval_points and <_PREFIX>find_roots (same signatures), and the two calls ComplexTracing
+    asks for over <_PREFIX>root_slopes and <_PREFIX>newton (sections 15 and 18): CylinderComplex and
     cylt_complex.RotatingCylinderComplex.  One ShootProblem per (mode, m), created on first use."""
     _PREFIX = None                                  # "es_cyl_complex_" / "es_cylt_complex_"
     P_TOL = 4.0                                     # acceptance of a refined root, percent: that of SlabComplexFlow
@@ -122,6 +123,13 @@ class CylinderEvaluation:
         w, row = roots["w"].cpu().numpy()[ok], roots["row"].cpu().numpy()[ok]
         return [_distinct(w[row == r]) for r in range(len(k))]
 
+    # ---- slopes and Newton tracing (C ABI sections 15 and 18): ComplexTracing over these two calls -------------------------
+    def _slopes_call(self, p, *args):
+        return self._entry("root_slopes")(self.ctx.handle, p.handle, *args)
+
+    def _newton_call(self, p, *args):
+        return self._entry("newton")(self.ctx.handle, p.handle, *args)
+
 
 class CylinderComplex(CylinderEvaluation, ComplexTracing):
     """D_c(k, omega) of one cylinder equilibrium at complex omega: grids, point lists, roots (CylinderEvaluation), and through
@@ -135,13 +143,6 @@ class CylinderComplex(CylinderEvaluation, ComplexTracing):
         if getattr(equilibrium, "twisted", True):
             raise TypeError("CylinderComplex takes an untwisted cylinder equilibrium (CylinderDensity, CylinderFlow)")
         self._init(equilibrium, ctx)
-
-    # ---- slopes and Newton tracing (C ABI section 15): ComplexTracing over these two calls ----------------------------------
-    def _slopes_call(self, p, *args):
-        return self.ctx.lib.es_cyl_complex_root_slopes(self.ctx.handle, p.handle, *args)
-
-    def _newton_call(self, p, *args):
-        return self.ctx.lib.es_cyl_complex_newton(self.ctx.handle, p.handle, *args)
 
     # ---- eigenfunctions and perturbation fields (C ABI section 16) -----------------------------------------------------
     def eigenfunction(self, mode, k, w, n_ext=500, m=None):

@@ -26,10 +26,3 @@ class RotatingCylinderComplex(CylinderEvaluation, ComplexTracing):
         if not getattr(equilibrium, "twisted", False):
             raise TypeError("RotatingCylinderComplex takes a twisted cylinder equilibrium (CylinderRotation)")
         self._init(equilibrium, ctx)
-
-    # ---- slopes and Newton tracing (C ABI section 18): ComplexTracing over these two calls ----------------------------------
-    def _slopes_call(self, p, *args):
-        return self.ctx.lib.es_cylt_complex_root_slopes(self.ctx.handle, p.handle, *args)
-
-    def _newton_call(self, p, *args):
-        return self.ctx.lib.es_cylt_complex_newton(self.ctx.handle, p.handle, *args)

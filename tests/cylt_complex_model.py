@@ -1,5 +1,5 @@
 """NumPy restatement of the complex-frequency determinant of the twisted (rotating) cylinder (include/eigensolver_amd.h section
-17, eigensolver_amd/csrc/es_cylt_complex.hip): test infrastructure, in the manner of tests/cyl_complex_model.py.
+17, eigensolver_amd/csrc/es_cyl_complex.hip at FAM_CYLT): test infrastructure, in the manner of tests/cyl_complex_model.py.
 
 Step for step what the kernel does, in plain complex128:
   * the 20 base fields es_problem_create forms from the 2N - 1 profile samples, the node entries and coefficients of the
