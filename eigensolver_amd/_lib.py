@@ -349,4 +349,8 @@ def _sig(lib):
     if hasattr(lib, "es_cylt_complex_root_slopes"):         # likewise
         lib.es_cylt_complex_root_slopes.argtypes = lib.es_cyl_complex_root_slopes.argtypes
         lib.es_cylt_complex_newton.argtypes = lib.es_cyl_complex_newton.argtypes
+    # (19) eigenfunctions of complex roots of the twisted cylinder: the signature of (16); its polarisation and synthesis calls
+    # take no problem handle and serve both families
+    if hasattr(lib, "es_cylt_complex_eigenfunction"):       # likewise
+        lib.es_cylt_complex_eigenfunction.argtypes = lib.es_cyl_complex_eigenfunction.argtypes
     return lib

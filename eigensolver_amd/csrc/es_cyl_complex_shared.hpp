@@ -5,7 +5,8 @@
 //   Z = esb::CJet<1>   value and d/d omega: the Newton steps of es_cyl_complex_slopes.hip (both families)
 //   Z = esb::CJet<2>   value, d/d omega and d/dk: the slopes
 // The wavenumber comes as K: a plain double where it is a constant of the differentiation (cz, CJet<1>), the jet (k, 0, 1)
-// for CJet<2>.  F defaults to FAM_CYL0, the untwisted cylinder: the translation units of section 16 name no family.
+// for CJet<2>.  F defaults to FAM_CYL0, the untwisted cylinder.  The eigenfunction march of sections 16 and 19
+// (es_cyl_complex_eigen.hip) uses cyl_exterior, cyl_stage_chunk and cyl_node of this text at Z = esb::cz, over F.
 //
 // Interior: the formula text of es_shoot_device.hpp for the family (make_entry, coef_pre, coef_finish, adjoint_start,
 // rk4_step_adjoint<SHAPE>, boundary_algebra) instantiated with Z, TRACK = false, the plain (not scaled, normalised) RK4 step, one
@@ -202,7 +203,7 @@ __device__ __forceinline__ CylcMatch<Z> cyl_shoot_point(const ShootDev& P, const
   return R;
 }
 
-// the family check of every entry point of sections 14 - 18
+// the family check of every entry point of sections 14 - 19
 template <int F = FAM> int check_cyl_cx(es_context* ctx, const es_problem* prob) {
   ES_REQUIRE(ctx, prob != nullptr, "null problem");
   if (prob->dev.family != F) {

@@ -131,27 +131,20 @@ class CylinderEvaluation:
         return self._entry("newton")(self.ctx.handle, p.handle, *args)
 
 
-class CylinderComplex(CylinderEvaluation, ComplexTracing):
-    """D_c(k, omega) of one cylinder equilibrium at complex omega: grids, point lists, roots (CylinderEvaluation), and through
-    ComplexTracing the slopes and the Newton tracing of section 15 -- root_slopes(mode, k, w, count=None, m=None),
-    group_velocity(mode, roots, count=None, m=None), newton(mode, k, w0, ..., m=None) and densify(mode, k, w, k_fine,
-    shift_factor=4.0, m=None, **newton_kw), with the return conventions of SlabComplexFlow."""
-    _SELECT = ("m",)
-    _PREFIX = "es_cyl_complex_"
+class CylinderEigenfunctions:
+    """What a mode looks like (C ABI sections 16 and 19), written once for CylinderComplex and
+    cylt_complex.RotatingCylinderComplex beside CylinderEvaluation: `eigenfunction` through <_PREFIX>eigenfunction (same
+    signature in both families), `polarisation` and `field_synthesis` through es_cyl_complex_polarisation and
+    es_cyl_complex_field_synthesis, which take no problem handle and serve both families, and `fields`."""
 
-    def __init__(self, equilibrium, ctx=None):
-        if getattr(equilibrium, "twisted", True):
-            raise TypeError("CylinderComplex takes an untwisted cylinder equilibrium (CylinderDensity, CylinderFlow)")
-        self._init(equilibrium, ctx)
-
-    # ---- eigenfunctions and perturbation fields (C ABI section 16) -----------------------------------------------------
     def eigenfunction(self, mode, k, w, n_ext=500, m=None):
-        """Two-region solution at the complex (k, omega) pairs (es_cyl_complex_eigenfunction).  `w` is complex and `k` is
-        broadcast against it; both may be tensors, e.g. roots["k"], roots["w"] of find_roots.  Dict of CUDA tensors as
-        SlabComplexFlow.eigenfunction: x_int [N], value_int / flux_int [n, N] (complex128: P and xi_r on the node grid, node 0 =
+        """Two-region solution at the complex (k, omega) pairs (es_cyl_complex_eigenfunction; es_cylt_complex_eigenfunction on
+        a twisted equilibrium).  `w` is complex and `k` is broadcast against it; both may be tensors, e.g. roots["k"],
+        roots["w"] of find_roots.  Dict of CUDA tensors as SlabComplexFlow.eigenfunction: x_int [N], value_int / flux_int [n, N] (complex128: P and xi_r on the node grid, node 0 =
         boundary), x_ext [n, n_ext], value_ext / flux_ext [n, n_ext] (complex128, far field to boundary), status [n] (uint8,
         that of eval_points; rows that are not ES_PT_OK are NaN).  Scaled per unit P_e(boundary): value_ext[:, -1] = 1,
-        value_int[:, 0] = 1 and flux_ext[:, -1] - flux_int[:, 0] = D_c."""
+        value_int[:, 0] = 1 and flux_ext[:, -1] - flux_int[:, 0] = D_c (to rounding where the axis target is zero, to the RK4
+        truncation of the grid on a twisted problem with bc_const != 0: section 19)."""
         import torch
         p, dk, dre, dim = self._pairs(mode, k, w, m=m)
         dev = dk.device
@@ -162,9 +155,8 @@ class CylinderComplex(CylinderEvaluation, ComplexTracing):
         ve = torch.empty((n, n_ext), dtype=torch.complex128, device=dev)
         fe = torch.empty((n, n_ext), dtype=torch.complex128, device=dev)
         st = torch.empty(n, dtype=torch.uint8, device=dev)
-        rc = self.ctx.lib.es_cyl_complex_eigenfunction(self.ctx.handle, p.handle, _lib.ptr(dk), _lib.ptr(dre), _lib.ptr(dim), n,
-                                                       _lib.ptr(vi), _lib.ptr(fi), n_ext, _lib.ptr(xe), _lib.ptr(ve),
-                                                       _lib.ptr(fe), _lib.ptr(st))
+        rc = self._entry("eigenfunction")(self.ctx.handle, p.handle, _lib.ptr(dk), _lib.ptr(dre), _lib.ptr(dim), n, _lib.ptr(vi),
+                                          _lib.ptr(fi), n_ext, _lib.ptr(xe), _lib.ptr(ve), _lib.ptr(fe), _lib.ptr(st))
         _lib.check(self.ctx.handle, rc)
         x_int = torch.linspace(p.desc.x_boundary, p.desc.x_end, N, dtype=torch.float64, device=dev)
         return dict(x_int=x_int, value_int=vi, flux_int=fi, x_ext=xe, value_ext=ve, flux_ext=fe, status=st)
@@ -237,3 +229,18 @@ class CylinderComplex(CylinderEvaluation, ComplexTracing):
             return out, carry or dict(points=pts)
 
         return _frame_chunks(synth, dt, frames_per_call, names)
+
+
+class CylinderComplex(CylinderEvaluation, CylinderEigenfunctions, ComplexTracing):
+    """D_c(k, omega) of one cylinder equilibrium at complex omega: grids, point lists, roots (CylinderEvaluation), and through
+    ComplexTracing the slopes and the Newton tracing of section 15 -- root_slopes(mode, k, w, count=None, m=None),
+    group_velocity(mode, roots, count=None, m=None), newton(mode, k, w0, ..., m=None) and densify(mode, k, w, k_fine,
+    shift_factor=4.0, m=None, **newton_kw), with the return conventions of SlabComplexFlow; through CylinderEigenfunctions
+    eigenfunction, polarisation, field_synthesis and fields of section 16."""
+    _SELECT = ("m",)
+    _PREFIX = "es_cyl_complex_"
+
+    def __init__(self, equilibrium, ctx=None):
+        if getattr(equilibrium, "twisted", True):
+            raise TypeError("CylinderComplex takes an untwisted cylinder equilibrium (CylinderDensity, CylinderFlow)")
+        self._init(equilibrium, ctx)

@@ -1090,8 +1090,11 @@ int es_cyl_complex_newton(es_context* ctx, const es_problem* prob,
  *       interior value at node 0 is 1 to rounding (beta imposes it), the exterior flux at the boundary is the `outer` of
  *       es_cyl_complex_eval_points, and
  *           exterior flux at the boundary - interior flux at node 0 = D_c.
- *       The outward RK4 step and the adjoint RK4 step of the determinant are transposes of each other step by step, so this
- *       holds to rounding (2e-15 of max(|outer|, |inner|) measured), not only to truncation as in section 5.
+ *       The adjoint RK4 row march of the determinant is J (outward RK4 march) J^-1 for the trace-free coefficient matrix,
+ *       so the two agree exactly where the axis target is zero: ES_AXIS_SAUSAGE, and ES_AXIS_KINK with bc_const = 0, which
+ *       is every untwisted reference problem.  There this holds to rounding (2e-15 of max(|outer|, |inner|) measured), not
+ *       only to truncation as in section 5.  With a non-zero target the two differ by (det S - 1) target / p2, S the
+ *       discrete outward transfer matrix, whose determinant RK4 keeps at 1 to truncation only (section 19).
  *       d_status[i] (may be NULL) is the status section 14 gives the pair: ES_PT_OK, ES_PT_LEAKY or ES_PT_NONFINITE.  A pair
  *       that is not ES_PT_OK gets NaN in every value and flux entry; its d_ext_x row is still written and the other pairs do
  *       not depend on it.  n_ext is 0 or >= 2; n == 0 succeeds and touches nothing.  Asynchronous on the context's stream
@@ -1116,8 +1119,9 @@ int es_cyl_complex_newton(es_context* ctx, const es_problem* prob,
  *     v_scale, ES_FIELD_Z_REFERENCE_ANGLE, ES_FIELD_BIG_ENDIAN, the size limits, the alignment rule (16-byte stores where the
  *     row is 16-byte aligned, 4-byte stores otherwise, the same bits either way), the empty-size and mask rules are those of
  *     section 7.
- *     Not offered: eigenfunctions and fields of the twisted cylinder at complex frequency (its determinant and roots:
- *     section 17); Cartesian sampling and vorticity (section 8) of unstable
+ *     (Eigenfunctions of the twisted cylinder at complex frequency: section 19; es_cyl_complex_polarisation and
+ *     es_cyl_complex_field_synthesis take no problem and serve both families.)
+ *     Not offered: Cartesian sampling and vorticity (section 8) of unstable
  *     cylinder modes; physically phased amplitudes (the i between the radial and the other components).
  * ====================================================================================================== */
 int es_cyl_complex_eigenfunction(es_context* ctx, const es_problem* prob,
@@ -1156,7 +1160,7 @@ int es_cyl_complex_field_synthesis(es_context* ctx, const double* d_radius, cons
  *     the signatures, the grid layout, w_mode, the cell rule, the secant refinement, the flag, the order of the table, the
  *     capacity convention and the argument checks are those of section 14, word for word.  A call with no points succeeds
  *     and touches nothing.  The eval calls are asynchronous on the context's stream; es_cylt_complex_find_roots synchronises.
- *     Not offered: eigenfunctions and fields (section 16) of twisted problems; m < 0.  (Slopes and Newton tracing: section 18.)
+ *     Not offered: m < 0.  (Slopes and Newton tracing: section 18; eigenfunctions and fields: section 19.)
  * ====================================================================================================== */
 int es_cylt_complex_eval_grid(es_context* ctx, const es_problem* prob, const double* d_k, int nk,
                               const double* d_w_re, int n_re, const double* d_w_im, int n_im, int w_mode,
@@ -1185,7 +1189,7 @@ int es_cylt_complex_find_roots(es_context* ctx, const es_problem* prob, const do
  *     The signatures, the output layouts ([3][n][2] outer / inner; w, resid, dwdk, iters, flag), d_count, the statuses, the
  *     NaN rule, the Newton rule (that of es_complex_newton, step for step), the flag, the argument checks and the
  *     asynchrony are those of section 15, word for word.
- *     Not offered: eigenfunctions and fields at complex roots of twisted problems; m < 0; second derivatives.
+ *     Not offered: m < 0; second derivatives.  (Eigenfunctions and fields at these roots: section 19.)
  * ====================================================================================================== */
 int es_cylt_complex_root_slopes(es_context* ctx, const es_problem* prob,
                                 const double* d_k, const double* d_w_re, const double* d_w_im, int n,
@@ -1199,6 +1203,55 @@ int es_cylt_complex_newton(es_context* ctx, const es_problem* prob,
                            int max_iter, double step_cap, double max_shift, double tol_percent,
                            double* d_w_re, double* d_w_im, double* d_resid,
                            double* d_dwdk /* [n][2], may be NULL */, int32_t* d_iters, int32_t* d_flag);
+
+/* ======================================================================================================
+ * (19) Eigenfunctions and perturbation fields of complex roots of the twisted (rotating) cylinder (the unstable modes of
+ *     sections 17 and 18): section 16 for ES_GEOM_CYLINDER_TWIST problems.  ES_GEOM_CYLINDER_TWIST problems only (m >= 0,
+ *     the three axis conditions, both values of c1_power, both signs of r); every other geometry gets ES_ERR_UNSUPPORTED
+ *     with the outputs untouched (the untwisted cylinder has section 16, whose call in turn keeps refusing twisted
+ *     problems).  DESIGN.md section 8n.
+ *
+ *     es_cylt_complex_eigenfunction: the signature, the layouts, the exterior, the normalisation P_e(boundary) = 1 + 0i,
+ *     the NaN rule, the argument checks, the asynchrony and the d_status = NULL scratch rule of
+ *     es_cyl_complex_eigenfunction, word for word; d_status[i] is the status section 17 gives the pair.
+ *       Interior: the discrete problem of section 5 for this family in complex arithmetic -- the node / mid-point
+ *       coefficient sets of section 17 (the 20-field base table, the general coefficient set with v_phi and B_phi, one
+ *       complex division per node), one classical RK4 step of the full 2x2 system per interval taken outwards,
+ *       y_j = S_j y_{j+1}, the axis condition at node N-1
+ *           ES_AXIS_KINK            P =   bc_const xi_e
+ *           ES_AXIS_ROTATION_KINK   P = -(bc_const xi_e)
+ *           ES_AXIS_SAUSAGE         (P, Xi) along (a12, -a11)     (P' = 0; a11 is not zero in this family)
+ *       and P = P_b at node 0; xi_r = Xi / r.  Its solution is the one section 16's two outward marches give in exact
+ *       arithmetic, but it is not formed that way: with a non-zero target (every ES_AXIS_ROTATION_KINK problem) a state
+ *       marched outwards grows like the regular solution r^m while the answer stays O(1), and P(r_b) = P_b came out of a
+ *       cancellation that left up to 1e-6 of rounding in fp64.  Three passes instead: g from d = (0, 1) (sausage:
+ *       (a12, -a11)) at the axis outwards, its raw state parked in the caller's own output rows; s from (0, 1) at the
+ *       boundary inwards by the exact inverse of the same step, s_{j+1} = S_j^-1 s_j; s once more with every node written as
+ *       a s_j + b g_j, b = P_b / P(g_0) and a = target / P(s_{N-1}) (sausage: a = 0).  So d_int_value and d_int_flux are
+ *       read as well as written by the call, and the interior value at node 0 is P_b = 1 to one rounding.
+ *       Exterior: the medium outside is the same; the exterior arrays are those of section 16.
+ *       The exterior value at the boundary is exactly 1, the exterior flux at the boundary is the `outer` of
+ *       es_cylt_complex_eval_points.  The identity
+ *           exterior flux at the boundary - interior flux at node 0 = D_c
+ *       holds to rounding for ES_AXIS_SAUSAGE and wherever the target is zero (bc_const = 0: the zero-twist limit), as in
+ *       section 16.  With a non-zero target -- every ES_AXIS_ROTATION_KINK problem of the family -- the adjoint row march
+ *       of the determinant and the outward step's solution differ by (det S - 1) target / p2, S the discrete outward transfer
+ *       matrix, whose determinant RK4 keeps at 1 only to truncation: the identity then holds to the RK4 truncation of the
+ *       grid, 1e-7 to 2e-4 of max(|outer|, |inner|) at N = 130 on the problems measured and smaller on a finer grid (the
+ *       table of DESIGN.md section 8n).  The eigenfunction is the outward step's; on the real axis it is that of section 5
+ *       wherever that march keeps its digits (3e-13 on the reference problem).
+ *
+ *     Amplitudes and frames: es_cyl_complex_polarisation and es_cyl_complex_field_synthesis (section 16) on these arrays;
+ *     they take no problem.  With the twisted es_field_profiles (v_phi and s_phi not zero) the T, Q, g and s_phi terms of
+ *     section 7's formulas take part with complex Om.
+ *     Not offered: Cartesian sampling and vorticity (section 8) of unstable modes; m < 0; physically phased amplitudes.
+ * ====================================================================================================== */
+int es_cylt_complex_eigenfunction(es_context* ctx, const es_problem* prob,
+                                  const double* d_k, const double* d_w_re, const double* d_w_im, int n,
+                                  double* d_int_value, double* d_int_flux,      /* n x N complex      */
+                                  int n_ext, double* d_ext_x,                   /* n x n_ext real     */
+                                  double* d_ext_value, double* d_ext_flux,      /* n x n_ext complex  */
+                                  uint8_t* d_status /* n, may be NULL */);
 
 #ifdef __cplusplus
 }
