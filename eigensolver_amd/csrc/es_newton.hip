@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64) void root_newton_kernel(ShootDev P, const doubl
     if (fabs(s) > step_cap) s = copysign(step_cap, s);
     w += s;
     ++iters;
-    if (fabs(s) <= 1e-14 * fmax(1.0, fabs(w))) break;
+    if (fabs(s) <= 1e-14 * fabs(w)) break;             // relative alone: an absolute floor would tie the rule to one unit system
   }
   // the final point: slopes in both variables, and the status es_shoot_eval_points gives the pair
   JetMatch<2> E;

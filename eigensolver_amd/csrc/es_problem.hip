@@ -143,6 +143,20 @@ extern "C" int es_problem_create(es_context* ctx, const es_shoot_desc* d, const 
   S.cT2_i = (S.S_i > 0.0) ? S.c2_i * S.vA2_i / S.S_i : 0.0;
   S.rho_i = d->rho_i;
   S.accept_norm = d->accept_norm;
+  {
+    // units of the fp32 screening march: V = 2^ev from the larger exterior speed, R = 4^er from the exterior density, by
+    // their binary exponents alone -- inputs rescaled by powers of two shift ev and er by exactly as much, and the march
+    // sees the same numbers.  The velocity scale stays 1 where the coefficients are not homogeneous in it (the reference's
+    // formulas): the flow slab with shear (D(x) of SF-G:423, G = S t^2 + k^4 cT^2 c^2) and the twisted cylinder with
+    // c1_power = 1 (C1 = Q Om - (2 m S / r^2) t2 T).
+    auto half_exp = [](double x) { return (x > 0.0 && std::isfinite(x)) ? (int)std::floor(0.5 * (double)ilogb(x)) : 0; };
+    bool homogeneous = true;
+    if (d->geometry == ES_GEOM_SLAB_FLOW)
+      for (int i = 0; i < npts; ++i) homogeneous = homogeneous && B(SF_DU, i) == 0.0 && B(SF_DDU, i) == 0.0;
+    if (d->geometry == ES_GEOM_CYLINDER_TWIST && d->c1_power != 2) homogeneous = false;
+    p->f32_ev = homogeneous ? half_exp(fmax(S.vAe2, S.ce2)) : 0;      // vAe2, ce2: speeds squared
+    p->f32_er = half_exp(S.rho_e);
+  }
   if (d->geometry == ES_GEOM_CYLINDER || d->geometry == ES_GEOM_SLAB_FLOW || d->geometry == ES_GEOM_SLAB_DENSITY) {
     // continuum bands in phase speed (band_crossed): node j is inside band t iff centre_j - a_j < W < centre_j + a_j
     //   cylinder:     centre = v_z, a = |bA| (Alfven), |bA| sqrt(q) (cusp)

@@ -118,6 +118,36 @@ struct RowBands {
 // per-row scalars of the flow slab in fp32 (KScal: k^2 c^2, k^2 vA^2, k^2 cT^2, k^4 cT^2 c^2; S_i)
 struct SlabScalF { float kc2, kvA2, kcT2, k4c, S; };
 
+// Units of the march.  The fp32 march runs on speeds / V and densities / R, V = 2^ev and R = 4^er chosen per problem
+// (es_problem::f32_ev, f32_er), so that its products (t1 t2 ~ omega^4, their product over two nodes ~ omega^8, C3 ~
+// rho^2 omega^8) stay inside the 8 bits of exponent whatever units the caller uses: with speeds in m/s the product of the
+// two denominators of a step overflowed, v_rcp_f32 returned 0 and the march went on with finite, wrong coefficients.
+// Node entry f of make_entry has the dimension speed^a density^b; entry_unit_exp is the binary exponent of V^a R^b.  The
+// entries are divided by it in fp64 before their one rounding to fp32, omega by V, the flow slab's row scalars alike; every
+// threshold after the march is formed from these normalised numbers.  A power of two changes no mantissa, so at any units
+// the march delivers what it delivers at the normalised ones.  What goes back to the fp64 boundary algebra is the adjoint
+// pair at its true scale: a12 = [u1]/[u2] per length has the dimension V^2 R (cylinders: P / xi_r), 1 / (V^2 R) (density
+// slab: Vx / (F Vx')) or none (flow slab), a21 the inverse, and with r1 = r1~ the second component is r2 = r2~ [u1]/[u2]
+// (ratio_unit_exp) for both start values of the march, (1, 0) and (a11, a12).
+template <int FAM>
+__device__ __forceinline__ int entry_unit_exp(int f, int ev, int er) {
+  if (FAM == FAM_CYL0) {
+    const int a[7] = {1, 2, 2, 0, -2, 0, 2}, b2[7] = {0, 0, 0, 2, -2, -2, -2};
+    return a[f] * ev + b2[f] * er;
+  } else if (FAM == FAM_CYLT) {
+    const int a[16] = {1, 2, 2, 2, 0, 2, 2, 3, 2, 1, 2, 2, 2, 2, 0, 0}, b2[16] = {0, 0, 0, 2, 2, 2, 2, 2, 2, 2, 0, 0, 2, 0, 0, 0};
+    return a[f] * ev + b2[f] * er;
+  } else if (FAM == FAM_SLABD) {
+    const int a[5] = {2, 2, 2, 2, 0}, b2[5] = {0, 0, 0, 2, 2};
+    return a[f] * ev + b2[f] * er;
+  }
+  return ev;                                           // flow slab: k U, k U', k U'', 2 k U'
+}
+template <int FAM>
+__device__ __forceinline__ int ratio_unit_exp(int ev, int er) {
+  return (FAM == FAM_CYL0 || FAM == FAM_CYLT) ? 2 * (ev + er) : (FAM == FAM_SLABD) ? -2 * (ev + er) : 0;
+}
+
 // C1P = c1_power of the twisted family as a template parameter: a runtime select between Om and Om^2 costs two
 // v_cndmask_b32 per pair and node (the kernel branches once per chunk instead).
 template <int FAM, bool TRACK, int C1P = 1>
@@ -314,7 +344,7 @@ __device__ __forceinline__ void f32_march_chunk(const float* lds, int nst, bool 
 template <int FAM, int PTS, int MAXT, bool TRACK, int WPE>
 __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, const double* __restrict__ wv, int nw,
-                           int w_mode, double* __restrict__ Dout, uint8_t* __restrict__ stout) {
+                           int w_mode, int ev, int er, double* __restrict__ Dout, uint8_t* __restrict__ stout) {
   static_assert(PTS % 2 == 0, "points are processed in pairs");
   constexpr int NP = PTS / 2;
   constexpr int NE = FamTraits<FAM>::NE;
@@ -331,7 +361,8 @@ void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, co
     const int w0 = seg * T * PTS;
     const double k = kv[row];
     const KScal s = make_kscal(P, k);
-    const SlabScalF ss = {(float)s.kc2, (float)s.kvA2, (float)s.kcT2, (float)s.k4c, (float)P.S_i};
+    const SlabScalF ss = {(float)ldexp(s.kc2, -2 * ev), (float)ldexp(s.kvA2, -2 * ev), (float)ldexp(s.kcT2, -2 * ev),
+                          (float)ldexp(s.k4c, -4 * ev), (float)ldexp(P.S_i, -2 * ev)};
     v2f wf[NP], zp[NP], zq[NP];
     int zexp[PTS];                                     // accumulated power-of-two scaling of (zp, zq), per point
     CoefF B0[NP], B1[NP];
@@ -341,7 +372,8 @@ void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, co
     for (int p = 0; p < PTS; ++p) {
       const int iw = w0 + p * T + (int)threadIdx.x;
       const double w = (iw < nw) ? pick_w(wv, w_mode, k, row, nw, iw) : 1.0;
-      if (p & 1) wf[p >> 1].y = (float)w; else wf[p >> 1].x = (float)w;
+      const float wn = (float)ldexp(w, -ev);            // omega / V
+      if (p & 1) wf[p >> 1].y = wn; else wf[p >> 1].x = wn;
       // m_e > 0 (evanescent exterior) and, for the band families, not inside a continuum band: worth a march
       const double Oe = (FAM == FAM_SLABD || FAM == FAM_SLABF) ? (w - k * P.U_e) : w;
       const double k2 = k * k, w2 = Oe * Oe;
@@ -364,7 +396,9 @@ void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, co
       for (int i = threadIdx.x; i < 2 * nst + ES_FAR_NODE(c, nchunks); i += T) {   // far node: first chunk only (es_shoot_grid_body.hpp)
         double b[FamTraits<FAM>::NB], e[NE];
         load_base<FAM>(P, 2 * c0 + i, b);
-        make_entry<FAM>(b, s, e);                      // fp64, rounded to fp32 once
+        make_entry<FAM>(b, s, e);                      // fp64, brought to the units of the march, rounded to fp32 once
+#pragma unroll
+        for (int f = 0; f < NE; ++f) e[f] = ldexp(e[f], -entry_unit_exp<FAM>(f, ev, er));
         float ef32[NES];
 #pragma unroll
         for (int f = 0; f < NES; ++f) ef32[f] = (f < NE) ? (float)e[f] : 0.0f;
@@ -392,17 +426,24 @@ void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, co
     double bf[FamTraits<FAM>::NB], ef[NE];
     load_base<FAM>(P, 0, bf);
     make_entry<FAM>(bf, s, ef);
-    double emid[3] = {0.0, 0.0, 0.0}, elast[3] = {0.0, 0.0, 0.0};     // e0, omega_A^2, omega_c^2 of two more sampled nodes
+    // the watched terms are judged in the units of the march: efn, emid, elast are entries 0 - 2 of the boundary node and of
+    // two more sampled nodes (e0, omega_A^2, omega_c^2; the slabs read efn[0] alone) over their units
+    double efn[3], emid[3] = {0.0, 0.0, 0.0}, elast[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int f = 0; f < 3; ++f) efn[f] = ldexp(ef[f], -entry_unit_exp<FAM>(f, ev, er));
     if (TRACK) {
       double et[NE];
       load_base<FAM>(P, P.npts / 2, bf);
       make_entry<FAM>(bf, s, et);
-      emid[0] = et[0]; emid[1] = et[1]; emid[2] = et[2];
+#pragma unroll
+      for (int f = 0; f < 3; ++f) emid[f] = ldexp(et[f], -entry_unit_exp<FAM>(f, ev, er));
       load_base<FAM>(P, P.npts - 1, bf);
       make_entry<FAM>(bf, s, et);
-      elast[0] = et[0]; elast[1] = et[1]; elast[2] = et[2];
+#pragma unroll
+      for (int f = 0; f < 3; ++f) elast[f] = ldexp(et[f], -entry_unit_exp<FAM>(f, ev, er));
       load_base<FAM>(P, 0, bf);
     }
+    const double r2_unit = ldexp(1.0, ratio_unit_exp<FAM>(ev, er));
 #pragma unroll
     for (int p = 0; p < PTS; ++p) {
       const int iw = w0 + p * T + (int)threadIdx.x;
@@ -418,9 +459,11 @@ void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, co
       ShootDev Pl = P;
       Pl.bc_const = P.bc_const_raw * ldexp(1.0, -zexp[p]);
       Pl.slab_sign = P.slab_sign * ldexp(1.0, -zexp[p]);          // slabs: (slab_sign - r1) / r2 with r = (r1, r2) 2^zexp
-      const Mismatch M = boundary_algebra<FAM>(Pl, s, w, X, (double)zpp, (double)zqq, ef);
-      // watched terms: certain sign / certain crossing / unsure (see ScreenF)
-      const float S = F32_TAU_NODE * (float)(w * w + ef[1]);
+      const double r1 = (double)zpp, r2 = (double)zqq * r2_unit;   // the adjoint pair at its true scale (up to 2^zexp)
+      const Mismatch M = boundary_algebra<FAM>(Pl, s, w, X, r1, r2, ef);
+      // watched terms: certain sign / certain crossing / unsure (see ScreenF), in the units of the march
+      const double wn = ldexp(w, -ev);
+      const float S = F32_TAU_NODE * (float)(wn * wn + efn[1]);
       bool crossed, node_unsure;
       if (!TRACK) {                                     // band families: the status is exact (fp64 test on W = omega/k)
         crossed = band_crossed(P, kx, w);
@@ -428,13 +471,13 @@ void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, co
         if (FAM == FAM_SLABD || FAM == FAM_SLABF) {
           // slabs: the smallest magnitude of a watched term over the nodes against tau x the scale of these terms
           // (omega^2 + k^2 c^2; the flow slab's omega is the Doppler-shifted one at the boundary)
-          const double Omb = (FAM == FAM_SLABF) ? (w - ef[0]) : w;
-          const float sz = (float)(Omb * Omb + ((FAM == FAM_SLABF) ? s.kc2 : ef[0]));
+          const double Omb = (FAM == FAM_SLABF) ? (wn - efn[0]) : wn;
+          const float sz = (float)(Omb * Omb + ((FAM == FAM_SLABF) ? ldexp(s.kc2, -2 * ev) : efn[0]));
           node_unsure = !crossed && !(mnp > F32_TAU_NODE * sz);
         } else {
         // an evaluated point with a coefficient close to a singular point: |t1 t2| below tau (omega^2 + omega_A^2)^2 at
         // some node, i.e. ONE of the two factors within tau of zero relative to its size
-        const float sz = (float)(w * w + ef[1]);
+        const float sz = (float)(wn * wn + efn[1]);
         node_unsure = !crossed && !(mnp > F32_TAU_NODE * sz * sz);
         }
       } else {
@@ -444,14 +487,14 @@ void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, co
         // inside the domain, seen at three sampled nodes (boundary, middle, far end: one of them certainly negative, another
         // certainly positive => ES_PT_CONTINUUM whatever happens in between -- most of a continuum band of a monotone
         // profile); anything else is the margin fp64 decides
-        const bool sure12 = bands.sign_of(0, w, (double)S) >= 0 && bands.sign_of(1, w, (double)S) >= 0;
+        const bool sure12 = bands.sign_of(0, wn, (double)S) >= 0 && bands.sign_of(1, wn, (double)S) >= 0;
         bool cross12 = false;
         if (!sure12) {
 #pragma unroll
           for (int t = 0; t < 2; ++t) {
-            const int s0 = RowBands::node_sign(w, (double)S, ef[0], sqrt(ef[1 + t]));
-            const int s1 = RowBands::node_sign(w, (double)S, emid[0], sqrt(emid[1 + t]));
-            const int s2 = RowBands::node_sign(w, (double)S, elast[0], sqrt(elast[1 + t]));
+            const int s0 = RowBands::node_sign(wn, (double)S, efn[0], sqrt(efn[1 + t]));
+            const int s1 = RowBands::node_sign(wn, (double)S, emid[0], sqrt(emid[1 + t]));
+            const int s2 = RowBands::node_sign(wn, (double)S, elast[0], sqrt(elast[1 + t]));
             cross12 = cross12 || ((s0 < 0 || s1 < 0 || s2 < 0) && (s0 > 0 || s1 > 0 || s2 > 0));
           }
         }
@@ -478,7 +521,7 @@ void shoot_grid_f32_kernel(ShootDev P, const double* __restrict__ kv, int nk, co
           // The same algebra with the sign of slab_sign chosen so that nothing cancels gives that magnitude.
           ShootDev Pb = Pl;
           Pb.slab_sign = (zpp >= 0.0f) ? -fabs(Pl.slab_sign) : fabs(Pl.slab_sign);
-          const Mismatch Mb = boundary_algebra<FAM>(Pb, s, w, X, (double)zpp, (double)zqq, ef);
+          const Mismatch Mb = boundary_algebra<FAM>(Pb, s, w, X, r1, r2, ef);
           scale = fmax(scale, fabs(Mb.inner));
         }
         unsure = node_unsure || !isfinite(M.d) || !(fabs(M.d) > F32_TAU_D * scale) ||
@@ -509,23 +552,23 @@ int launch_grid_f32(es_context* ctx, const es_problem* prob, const double* d_k, 
       if (const char* ev = getenv("ES_F32_VARIANT")) v0 = atoi(ev);             // tuning aid
       if (bands && v0 == 1)
         hipLaunchKernelGGL((shoot_grid_f32_kernel<FAM, PTS, 256, false, 3>), grid, dim3(T), 0, ctx->stream,
-                           prob->dev, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+                           prob->dev, d_k, nk, d_w, nw, w_mode, prob->f32_ev, prob->f32_er, d_D, d_status);
       else if (bands && v0 == 2)
         hipLaunchKernelGGL((shoot_grid_f32_kernel<FAM, PTS, 256, false, 2>), grid, dim3(T), 0, ctx->stream,
-                           prob->dev, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+                           prob->dev, d_k, nk, d_w, nw, w_mode, prob->f32_ev, prob->f32_er, d_D, d_status);
       else if (bands && v0 == 3) {
         int T8 = ((nw + 7) / 8 + 63) / 64 * 64;
         if (T8 < 64) T8 = 64;
         if (T8 > 256) T8 = 256;
         const long t8 = (long)nk * ((nw + T8 * 8 - 1) / (T8 * 8));
         hipLaunchKernelGGL((shoot_grid_f32_kernel<FAM, 8, 256, false, 2>), es_tile_grid(t8),
-                           dim3(T8), 0, ctx->stream, prob->dev, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+                           dim3(T8), 0, ctx->stream, prob->dev, d_k, nk, d_w, nw, w_mode, prob->f32_ev, prob->f32_er, d_D, d_status);
       } else if (bands)
         hipLaunchKernelGGL((shoot_grid_f32_kernel<FAM, PTS, 256, false, 4>), grid, dim3(T), 0, ctx->stream,
-                           prob->dev, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+                           prob->dev, d_k, nk, d_w, nw, w_mode, prob->f32_ev, prob->f32_er, d_D, d_status);
       else
         hipLaunchKernelGGL((shoot_grid_f32_kernel<FAM, PTS, 256, true, 4>), grid, dim3(T), 0, ctx->stream,
-                           prob->dev, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+                           prob->dev, d_k, nk, d_w, nw, w_mode, prob->f32_ev, prob->f32_er, d_D, d_status);
     } else {
       // measured on configs[4] (1024^2, N = 2000), packed fp32: 4 points per lane at 2 waves per SIMD (no spills) 4.5 ms;
       // the same capped at 168 registers (3 waves, spills) 5.6 ms; 2 points per lane at 4 waves 4.7 ms; fp64 9.4 ms
@@ -533,17 +576,17 @@ int launch_grid_f32(es_context* ctx, const es_problem* prob, const double* d_k, 
       if (const char* ev = getenv("ES_F32_VARIANT")) variant = atoi(ev);        // tuning aid
       if (variant == 1) {
         hipLaunchKernelGGL((shoot_grid_f32_kernel<FAM, PTS, 256, true, 2>), grid, dim3(T), 0, ctx->stream,
-                           prob->dev, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+                           prob->dev, d_k, nk, d_w, nw, w_mode, prob->f32_ev, prob->f32_er, d_D, d_status);
       } else if (variant == 2) {
         int T2 = ((nw + 1) / 2 + 63) / 64 * 64;
         if (T2 < 64) T2 = 64;
         if (T2 > 256) T2 = 256;
         const long tiles2 = (long)nk * ((nw + T2 * 2 - 1) / (T2 * 2));
         hipLaunchKernelGGL((shoot_grid_f32_kernel<FAM, 2, 256, true, 4>), es_tile_grid(tiles2),
-                           dim3(T2), 0, ctx->stream, prob->dev, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+                           dim3(T2), 0, ctx->stream, prob->dev, d_k, nk, d_w, nw, w_mode, prob->f32_ev, prob->f32_er, d_D, d_status);
       } else {
         hipLaunchKernelGGL((shoot_grid_f32_kernel<FAM, PTS, 256, true, 3>), grid, dim3(T), 0, ctx->stream,
-                           prob->dev, d_k, nk, d_w, nw, w_mode, d_D, d_status);
+                           prob->dev, d_k, nk, d_w, nw, w_mode, prob->f32_ev, prob->f32_er, d_D, d_status);
       }
     }
     es_timer_end(ctx);
@@ -564,7 +607,7 @@ int launch_grid_f32(es_context* ctx, const es_problem* prob, const double* d_k, 
     const long tiles = (long)nk * ((nw + T * PTS - 1) / (T * PTS));
     const dim3 grid = es_tile_grid(tiles);
     hipLaunchKernelGGL((shoot_grid_f32_kernel<FAM, PTS, 256, false, 3>), grid, dim3(T), 0, ctx->stream, prob->dev, d_k,
-                       nk, d_w, nw, w_mode, d_D, d_status);
+                       nk, d_w, nw, w_mode, prob->f32_ev, prob->f32_er, d_D, d_status);
     es_timer_end(ctx);
     ES_HIP_CHECK(ctx, hipGetLastError());
     return ES_SUCCESS;

@@ -9,6 +9,9 @@ struct es_problem {
   ShootDev dev;
   double* d_base = nullptr;
   es_shoot_desc desc;
+  // units of the fp32 screening march (es_screen.hip): it runs on speeds / 2^f32_ev and densities / 4^f32_er, powers of two
+  // chosen once from the exterior medium (es_problem_create) so that the march sees O(1) numbers whatever units the caller uses
+  int f32_ev = 0, f32_er = 0;
 };
 
 // `return CALL(FAM)` with the family of a problem as the template argument

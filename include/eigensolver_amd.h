@@ -116,7 +116,22 @@ enum { ES_W_ABSOLUTE = 0,      /* omega = w[iw]                       (one frequ
        ES_W_PHASE_SPEED = 1,   /* omega = k * w[iw]                   (the reference's bands speeds*k)      */
        ES_W_PER_ROW = 2 };     /* omega = w[ik * nw + iw]             (one frequency array per task)        */
 
-/* Everything a reference worker captures from module globals. */
+/* Everything a reference worker captures from module globals.
+ *
+ * Units.  The speeds, densities and fields of es_shoot_desc, es_profiles and es_cyl_uniform_params are dimensional and are used
+ * as given: nothing normalises them (lengths are in units of the half-width / radius: x_boundary = -1 or +1).  The results
+ * follow scaling laws: with every speed times V and every density times R (B_z, B_phi times V sqrt(R); rdC3 and bc_const times
+ * V^2 R; omega times V; k unchanged), D, outer and inner of a cylinder come out times 1 / (V^2 R) and those of a slab times V R,
+ * d/d omega takes one V off, roots and group speeds come out times V, rel, resid, statuses, flags, node and iteration counts
+ * do not change -- bit for bit when V and sqrt(R) are powers of two (DESIGN.md section 4e has the table;
+ * tests/test_unit_scaling_*.py).  Tested range: V in [2^-20, 2^20] and R in [4^-20, 4^20] around the reference's
+ * normalisation (speeds, densities and omega of order 1), the fp32 screening of es_shoot_find_roots_mixed included, which
+ * marches in units it derives from vA_e, c_e and rho_e.
+ * Exception: the flow slab with shear (ES_GEOM_SLAB_FLOW with dU != 0, and section 6 on such a profile) is not homogeneous in
+ * the velocity scale -- the reference's D(x), flow_multiprocessor_coronal.py:423, adds Omega^2 - k^2 cT^2 to a term without
+ * dimension of speed -- and must be given in the reference's normalised speeds; it follows the density scale.
+ * Beyond V = 2^+-40 the shared reciprocal of the flow slab's denominators leaves the fp64 range: measured on the CPU port of
+ * these kernels, finite wrong D with ES_PT_OK at V = 2^40 (uniform-flow slab), ES_PT_NONFINITE everywhere at V = 2^-40. */
 typedef struct es_shoot_desc {
   int32_t geometry;        /* ES_GEOM_*                                                                   */
   int32_t n_nodes;         /* interior nodes N: the reference's `ix` grid (linspace(x_b, x_end, N)); the
@@ -952,7 +967,8 @@ int es_complex_newton(es_context* ctx, const es_problem* prob, int variant,
  *             if status != ES_PT_OK or D, D_w not finite or D_w == 0:  ok = false; stop
  *             s = -D / D_w;  if |s| > step_cap: s = copysign(step_cap, s)
  *             w += s; iters += 1
- *             if |s| <= 1e-14 max(1, |w|): stop
+ *             if |s| <= 1e-14 |w|: stop            (relative alone: the rule does not depend on the unit of omega; section
+ *                                                   12's complex rule still has the floor max(1, |w|))
  *         at the final w (the jets of section 11, and the continuum looked at):
  *             scale = |outer| (problems with accept_norm) or max(|outer|, |inner|)        -- the rel of section 2
  *             resid = 100 |D| / scale,  dwdk = -D_k / D_w,  status

@@ -3,7 +3,7 @@
   exterior_status  ES_PT_OK / LEAKY / NONFINITE of the closed-form exterior, as the kernels decide it.
   newton_model     the iteration rule of es_shoot_newton, step for step, on root_slope_model.jets (complex-step derivatives: a
                    different route from the kernel's forward-mode jets); records the length of every step per lane.
-  clear            which lanes the GPU test may compare `iters` on: the rule stops a lane when |s| <= 1e-14 max(1, |w|), and a
+  clear            which lanes the GPU test may compare `iters` on: the rule stops a lane when |s| <= 1e-14 |w|, and a
                    step within a factor 10 of that threshold can fall on either side of it in another arithmetic.
   hermite          the Hermite prediction and the default shift bound of ShootProblem.densify in NumPy.
   port_root_near   the C port's root next to a candidate; the window of root_slope_model._port_root_near shifted off the
@@ -101,7 +101,7 @@ def newton_model(name, k, guess, max_iter=8, step_cap=np.inf, max_shift=np.inf, 
                 w[lane] += s
                 iters[lane] += 1
                 steps[lane].append(abs(s))
-                if abs(s) <= STOP * max(1.0, abs(w[lane])):
+                if abs(s) <= STOP * abs(w[lane]):
                     active[lane] = False
         o, i = R.jets(name, k, w)
         st = exterior_status(name, k, w)
@@ -116,7 +116,7 @@ def newton_model(name, k, guess, max_iter=8, step_cap=np.inf, max_shift=np.inf, 
 
 def clear(steps, w):
     """no step of the lane within a factor 10 of the stopping threshold"""
-    thr = STOP * max(1.0, abs(w))
+    thr = STOP * abs(w)
     return all(not (0.1 <= s / thr <= 10.0) for s in steps)
 
 
