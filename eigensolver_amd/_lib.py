@@ -231,6 +231,7 @@ FIELD_REFERENCE, FIELD_Z_REFERENCE_ANGLE, FIELD_BIG_ENDIAN = 1, 2, 4
 # ---- Cartesian sampling and vorticity (section 8) ----------------------------------------------------------------
 VORT_NAMES = ("Wr_C", "Wr_S", "Wphi_C", "Wphi_S", "Wz_C")                                     # ES_VORT_*
 CVAR_NAMES = ("P_T", "xi_x", "xi_y", "xi_z", "v_x", "v_y", "v_z", "vort_x", "vort_y", "vort_z")   # ES_CVAR_* (mask bits)
+CVORT_NAMES = ("W_r", "W_phi", "W_z")                                                         # ES_CVORT_* (section 20, complex)
 # ---- perturbation fields of a slab mode (section 9) --------------------------------------------------------------
 _SLAB_FIELD_PROFILE_FIELDS = ("rho", "c2", "vA2", "U", "dU")
 
@@ -353,4 +354,9 @@ def _sig(lib):
     # take no problem handle and serve both families
     if hasattr(lib, "es_cylt_complex_eigenfunction"):       # likewise
         lib.es_cylt_complex_eigenfunction.argtypes = lib.es_cyl_complex_eigenfunction.argtypes
+    # (20) Cartesian sampling and vorticity of complex cylinder roots: the signatures of (8) with complex tables and w_re, w_im
+    if hasattr(lib, "es_cyl_complex_vorticity_amplitudes"):  # likewise
+        lib.es_cyl_complex_vorticity_amplitudes.argtypes = [vp, vp, vp, i, i, i, i, vp, vp]
+        lib.es_cyl_complex_cartesian_synthesis.argtypes = [vp, vp, vp, vp, i, i, i, d, d, d, vp, i, vp, i, vp, i, vp, i,
+                                                           C.c_uint32, d, C.c_float, i, vp]
     return lib

@@ -8,7 +8,8 @@ both signs of r.  Shapes and return conventions are those of complex_flow.SlabCo
 D_w, D_k of a root, Newton's iteration and `densify`, which turns a few unstable_roots rows into the growth-rate curve that
 postprocess.most_unstable reads.  Section 16 adds what the mode looks like: `eigenfunction` (P and xi_r at complex roots),
 `polarisation` (the seven complex amplitudes) and `fields` (growing float32 frames ready for postprocess.write_vtk_frames).
-DESIGN.md sections 8i, 8j and 8k.
+Section 20 puts the mode on a Cartesian mesh with the vorticity of its velocity: `vorticity_amplitudes`, `cartesian_synthesis`
+and `cartesian_fields` (ready for postprocess.write_vtk_rectilinear_frames).  DESIGN.md sections 8i, 8j, 8k and 8o.
 """
 import ctypes as C
 
@@ -16,7 +17,8 @@ import numpy as np
 
 from . import _lib
 from .complex_flow import ComplexTracing, _distinct
-from .shooting import ShootProblem, W_ABSOLUTE, W_PHASE_SPEED, _frame_chunks, _frames_out, var_mask  # noqa: F401
+from .shooting import (ShootProblem, W_ABSOLUTE, W_PHASE_SPEED, _frame_chunks, _frames_out,  # noqa: F401
+                       _require_exterior_points, cartesian_var_mask, var_mask)
 
 
 class CylinderEvaluation:
@@ -131,11 +133,51 @@ class CylinderEvaluation:
         return self._entry("newton")(self.ctx.handle, p.handle, *args)
 
 
+def vorticity_amplitudes(ctx, radius, amp, n_nodes, n_ext, m, k):
+    """es_cyl_complex_vorticity_amplitudes on the tables of es_cyl_complex_polarisation (radius [n, n_r] and k [n] float64,
+    amp [n, 7, n_r] complex128, CUDA, n_r = n_nodes + n_ext): the three complex radial amplitudes of curl v, vort [n, 3, n_r]
+    complex128 in the order _lib.CVORT_NAMES, as shooting.vorticity_amplitudes.  Enqueued on the context's stream."""
+    import torch
+    n, n_r = radius.shape
+    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (n, 7, n_r) and k.shape == (n,)
+    for a, dt in ((radius, torch.float64), (amp, torch.complex128), (k, torch.float64)):
+        assert a.is_cuda and a.dtype == dt and a.is_contiguous()
+    vort = torch.empty((n, 3, n_r), dtype=torch.complex128, device=radius.device)
+    rc = ctx.lib.es_cyl_complex_vorticity_amplitudes(ctx.handle, _lib.ptr(radius), _lib.ptr(amp), n, int(n_nodes), int(n_ext),
+                                                     int(m), _lib.ptr(k), _lib.ptr(vort))
+    _lib.check(ctx.handle, rc)
+    return vort
+
+
+def cartesian_synthesis(ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z, t, variables=None, v_scale=1.0,
+                        fill=float("nan"), flags=0, out=None):
+    """es_cyl_complex_cartesian_synthesis for the tables of one mode (radius [n_r] float64, amp [7, n_r] and vort [3, n_r]
+    complex128 or None, CUDA; w complex): float32 frames out[n_t, n_sel, n_z, n_y, n_x] in the order of
+    cartesian_var_mask(variables)[1], as shooting.cartesian_synthesis.  Enqueued on the context's stream; returns (out, names)."""
+    import torch
+    mask, names = cartesian_var_mask(variables)
+    n_r = radius.numel()
+    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (7, n_r) and (vort is None or vort.shape == (3, n_r))
+    for a, dt in ((radius, torch.float64), (amp, torch.complex128), (vort, torch.complex128), (x, torch.float64),
+                  (y, torch.float64), (z, torch.float64), (t, torch.float64)):
+        assert a is None or (a.is_cuda and a.dtype == dt and a.is_contiguous())
+    out = _frames_out(out, (t.numel(), len(names), z.numel(), y.numel(), x.numel()), radius.device)
+    w = complex(w)
+    rc = ctx.lib.es_cyl_complex_cartesian_synthesis(ctx.handle, _lib.ptr(radius), _lib.ptr(amp),
+                                                    _lib.ptr(vort) if vort is not None else None, int(n_nodes), int(n_ext),
+                                                    int(m), float(k), w.real, w.imag, _lib.ptr(x), x.numel(), _lib.ptr(y),
+                                                    y.numel(), _lib.ptr(z), z.numel(), _lib.ptr(t), t.numel(), mask,
+                                                    float(v_scale), float(fill), int(flags), _lib.ptr(out))
+    _lib.check(ctx.handle, rc)
+    return out, names
+
+
 class CylinderEigenfunctions:
     """What a mode looks like (C ABI sections 16 and 19), written once for CylinderComplex and
     cylt_complex.RotatingCylinderComplex beside CylinderEvaluation: `eigenfunction` through <_PREFIX>eigenfunction (same
     signature in both families), `polarisation` and `field_synthesis` through es_cyl_complex_polarisation and
-    es_cyl_complex_field_synthesis, which take no problem handle and serve both families, and `fields`."""
+    es_cyl_complex_field_synthesis, which take no problem handle and serve both families, and `fields`; on the Cartesian mesh
+    (section 20) `vorticity_amplitudes`, `cartesian_synthesis` and `cartesian_fields`, likewise without a problem handle."""
 
     def eigenfunction(self, mode, k, w, n_ext=500, m=None):
         """Two-region solution at the complex (k, omega) pairs (es_cyl_complex_eigenfunction; es_cylt_complex_eigenfunction on
@@ -230,13 +272,62 @@ class CylinderEigenfunctions:
 
         return _frame_chunks(synth, dt, frames_per_call, names)
 
+    # ---- Cartesian sampling and vorticity (C ABI section 20) -------------------------------------------------------------
+    def vorticity_amplitudes(self, mode, k, w, n_ext=500, reference_quirks=False, m=None):
+        """`polarisation` followed by es_cyl_complex_vorticity_amplitudes: its dict with vort [n, 3, n_r] (complex128, channels
+        _lib.CVORT_NAMES) added, the complex radial amplitudes of curl v: omega_r = Re[W_r sin(m theta) e^{i (k z - w t)}],
+        omega_phi with cos(m theta), omega_z with sin(m theta).  Radial derivatives per region, never across the interface.
+        The exterior, when present, needs n_ext >= 3."""
+        import torch
+        p, dk, dre, dim = self._pairs(mode, k, w, m=m)          # on the device once: _pairs takes tensors as they are
+        p._require_positive_cylinder()
+        _require_exterior_points(n_ext)
+        pol = self.polarisation(mode, dk, torch.complex(dre, dim), n_ext=n_ext, reference_quirks=reference_quirks, m=m)
+        pol["vort"] = vorticity_amplitudes(self.ctx, pol["radius"], pol["amp"], int(p.desc.n_nodes), int(n_ext), int(p.desc.m), dk)
+        return pol
+
+    def cartesian_synthesis(self, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z, t, variables=None, v_scale=1.0,
+                            fill=float("nan"), flags=0, out=None):
+        """The module's cartesian_synthesis on this object's context.  Returns (out, names)."""
+        return cartesian_synthesis(self.ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z, t, variables, v_scale, fill,
+                                   flags, out)
+
+    def cartesian_fields(self, mode, k, w, x, y, z, t, variables=None, v_scale=1.0, fill=float("nan"), big_endian=False,
+                         frames_per_call=None, n_ext=500, reference_quirks=False, m=None):
+        """Fields of ONE complex root (k, omega) on the Cartesian mesh (x, y, z, t), the vorticity of the velocity and the
+        growth factor e^{Im w t} included: the dict of ShootProblem.cartesian_fields -- x, y, z, t, names, frames [n_t, n_sel,
+        n_z, n_y, n_x], <name>: frames[:, i], float32 CUDA tensors in the point order of a legacy-VTK RECTILINEAR_GRID -- or
+        with frames_per_call the generator of such dicts.  `variables`, `fill`, `v_scale`, `reference_quirks` as there.
+        big_endian: ready for postprocess.write_vtk_rectilinear_frames.  Positive radii (r_sign=+1) only."""
+        p = self.problem(mode, m)
+        p._require_positive_cylinder()
+        if np.ndim(k) != 0 or np.ndim(w) != 0:
+            raise ValueError("cartesian_fields() takes one root: scalar k and omega")
+        _require_exterior_points(n_ext)
+        k, w = float(k), complex(w)
+        mask, names = cartesian_var_mask(variables)
+        want_vort = any(v.startswith("vort_") for v in names)
+        tables = self.vorticity_amplitudes if want_vort else self.polarisation
+        tab = tables(mode, [k], [w], n_ext=n_ext, reference_quirks=reference_quirks, m=m)
+        radius, amp = tab["radius"][0], tab["amp"][0]
+        vort = tab["vort"][0] if want_vort else None
+        dx, dy, dz, dt = (p._dev(a).reshape(-1) for a in (x, y, z, t))
+        flags = _lib.FIELD_BIG_ENDIAN if big_endian else 0
+
+        def synth(t_part, _):
+            return self.cartesian_synthesis(radius, amp, vort, int(p.desc.n_nodes), int(n_ext), int(p.desc.m), k, w, dx, dy,
+                                            dz, t_part, names, v_scale, fill, flags)[0], {}
+
+        return _frame_chunks(synth, dt, frames_per_call, names, x=dx, y=dy, z=dz)
+
 
 class CylinderComplex(CylinderEvaluation, CylinderEigenfunctions, ComplexTracing):
     """D_c(k, omega) of one cylinder equilibrium at complex omega: grids, point lists, roots (CylinderEvaluation), and through
     ComplexTracing the slopes and the Newton tracing of section 15 -- root_slopes(mode, k, w, count=None, m=None),
     group_velocity(mode, roots, count=None, m=None), newton(mode, k, w0, ..., m=None) and densify(mode, k, w, k_fine,
     shift_factor=4.0, m=None, **newton_kw), with the return conventions of SlabComplexFlow; through CylinderEigenfunctions
-    eigenfunction, polarisation, field_synthesis and fields of section 16."""
+    eigenfunction, polarisation, field_synthesis and fields of section 16, vorticity_amplitudes, cartesian_synthesis and
+    cartesian_fields of section 20."""
     _SELECT = ("m",)
     _PREFIX = "es_cyl_complex_"
 

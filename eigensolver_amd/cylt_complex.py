@@ -20,8 +20,9 @@ class RotatingCylinderComplex(CylinderEvaluation, CylinderEigenfunctions, Comple
     parts=False), find_roots and unstable_roots as CylinderComplex has them, through ComplexTracing the slopes and the
     Newton tracing of section 18 -- root_slopes(mode, k, w, count=None, m=None), group_velocity(mode, roots, count=None,
     m=None), newton(mode, k, w0, ..., m=None) and densify(mode, k, w, k_fine, shift_factor=4.0, m=None, **newton_kw) --, and
-    through CylinderEigenfunctions eigenfunction, polarisation, field_synthesis and fields of section 19, with the arguments
-    and return dicts of CylinderComplex."""
+    through CylinderEigenfunctions eigenfunction, polarisation, field_synthesis and fields of section 19 and
+    vorticity_amplitudes, cartesian_synthesis and cartesian_fields of section 20, with the arguments and return dicts of
+    CylinderComplex."""
     _SELECT = ("m",)
     _PREFIX = "es_cylt_complex_"
 

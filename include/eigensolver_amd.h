@@ -1137,8 +1137,8 @@ int es_cyl_complex_newton(es_context* ctx, const es_problem* prob,
  *     section 7.
  *     (Eigenfunctions of the twisted cylinder at complex frequency: section 19; es_cyl_complex_polarisation and
  *     es_cyl_complex_field_synthesis take no problem and serve both families.)
- *     Not offered: Cartesian sampling and vorticity (section 8) of unstable
- *     cylinder modes; physically phased amplitudes (the i between the radial and the other components).
+ *     (Cartesian sampling and vorticity of these modes, section 8 at complex frequency: section 20.)
+ *     Not offered: physically phased amplitudes (the i between the radial and the other components).
  * ====================================================================================================== */
 int es_cyl_complex_eigenfunction(es_context* ctx, const es_problem* prob,
                                  const double* d_k, const double* d_w_re, const double* d_w_im, int n,
@@ -1260,7 +1260,8 @@ int es_cylt_complex_newton(es_context* ctx, const es_problem* prob,
  *     Amplitudes and frames: es_cyl_complex_polarisation and es_cyl_complex_field_synthesis (section 16) on these arrays;
  *     they take no problem.  With the twisted es_field_profiles (v_phi and s_phi not zero) the T, Q, g and s_phi terms of
  *     section 7's formulas take part with complex Om.
- *     Not offered: Cartesian sampling and vorticity (section 8) of unstable modes; m < 0; physically phased amplitudes.
+ *     (Cartesian sampling and vorticity of these modes: section 20, which takes no problem either.)
+ *     Not offered: m < 0; physically phased amplitudes.
  * ====================================================================================================== */
 int es_cylt_complex_eigenfunction(es_context* ctx, const es_problem* prob,
                                   const double* d_k, const double* d_w_re, const double* d_w_im, int n,
@@ -1268,6 +1269,57 @@ int es_cylt_complex_eigenfunction(es_context* ctx, const es_problem* prob,
                                   int n_ext, double* d_ext_x,                   /* n x n_ext real     */
                                   double* d_ext_value, double* d_ext_flux,      /* n x n_ext complex  */
                                   uint8_t* d_status /* n, may be NULL */);
+
+/* ======================================================================================================
+ * (20) Cartesian sampling of an unstable cylinder mode, with its vorticity: section 8 at complex frequency, on the complex
+ *     amplitude tables of es_cyl_complex_polarisation (section 16).  Neither call takes a problem, so both serve the
+ *     untwisted cylinder (sections 14 - 16) and the twisted one (sections 17 - 19).  DESIGN.md section 8o.
+ *
+ *     Convention: section 16's.  Every field is Re[A(r) Theta(theta) e^{i (k z - w t)}], w = w_re + i w_im, with the angular
+ *     factors of sections 7 / 8; with
+ *       EC = e^{w_im t} cos(k z - w_re t),    ES = e^{w_im t} sin(k z - w_re t)
+ *     its value is A_re (Theta EC) - A_im (Theta ES).  With d/dz -> i k the curl of
+ *       (v_r, v_phi, v_z) = Re[(a_r cos(m theta), a_phi (-sin(m theta)), a_z cos(m theta)) e^{i (k z - w t)}]
+ *     has three complex radial amplitudes (the growth factor depends on t alone and does not enter):
+ *       w_r   = Re[W_r   sin(m theta) e^{i (k z - w t)}]      W_r   = -m a_z / r + i k a_phi
+ *       w_phi = Re[W_phi cos(m theta) e^{i (k z - w t)}]      W_phi = -a_z' + i k a_r
+ *       w_z   = Re[W_z   sin(m theta) e^{i (k z - w t)}]      W_z   = (m a_r - a_phi - r a_phi') / r
+ *     On a real table this is section 8: Re W = (Wr_C, Wphi_C, Wz_C), Im W = (-Wr_S, -Wphi_S, 0).
+ *
+ *     es_cyl_complex_vorticity_amplitudes: d_radius [n x n_r] real, d_amp [n x 7 x n_r] complex exactly as
+ *     es_cyl_complex_polarisation writes them (interleaved (re, im) pairs), d_k [n]  ->
+ *     d_vort[((i * 3 + c) * n_r + j) * 2 + {re, im}], channels c = ES_CVORT_*.  One lane per (mode, radial point).  The radial
+ *     derivatives are those of es_cyl_vorticity_amplitudes -- np.gradient(a, r, edge_order=2) of each region on its own, in
+ *     its coefficient form -- applied to the real and the imaginary part separately; each part keeps section 8's grouping, so
+ *     that on a table with zero imaginary parts the values are section 8's.  A region that is present needs >= 3 points
+ *     (argument error otherwise); n_nodes = 0 or n_ext = 0 leaves that region out.  NaN / inf amplitudes, in either part,
+ *     reach the nodes whose stencil touches them and no others.  n == 0 is a successful call that touches nothing.
+ *     Asynchronous on the context's stream.
+ *
+ *     es_cyl_complex_cartesian_synthesis: the complex tables of ONE mode, d_amp [7 x n_r x 2] and d_vort [3 x n_r x 2]
+ *     (d_vort may be NULL if no vorticity bit is set)  ->  d_out [n_t][n_sel][n_z][n_y][n_x] float32.  Variables and mask:
+ *     ES_CVAR_* of section 8.  Everything of es_cyl_cartesian_synthesis carries over: the regions and the tie rule, the
+ *     bisection, the linear interpolation (of real and imaginary parts), `fill` as bits, ES_FIELD_BIG_ENDIAN as the only flag
+ *     (ES_FIELD_Z_REFERENCE_ANGLE is an argument error), 16-byte stores where every plane starts on a 16-byte boundary and
+ *     4-byte stores otherwise with the same bits, 4-byte alignment of d_out, the size limits, the empty sizes, the
+ *     argument errors, the asynchrony.  Per point and variable a complex coefficient c is formed, part by part exactly as
+ *     section 8 forms its real one (the (A * v_scale) * cos(m theta) grouping and the rotations to x, y included), and the
+ *     value is c_re EC - c_im ES, fp64 throughout, rounded once.  At w_im = 0 and with zero imaginary parts this is section
+ *     8's expression, grouping included: the same frames.  The launch shape is that of es_cyl_cartesian_split.
+ *     Not offered: m < 0; physically phased amplitudes.
+ * ====================================================================================================== */
+enum { ES_CVORT_R = 0, ES_CVORT_PHI, ES_CVORT_Z, ES_CVORT_COUNT };
+
+int es_cyl_complex_vorticity_amplitudes(es_context* ctx, const double* d_radius /* n x n_r */,
+                                        const double* d_amp /* n x 7 x n_r complex */, int n, int n_nodes, int n_ext,
+                                        int m, const double* d_k /* n */, double* d_vort /* n x 3 x n_r complex */);
+
+int es_cyl_complex_cartesian_synthesis(es_context* ctx, const double* d_radius, const double* d_amp /* 7 x n_r complex */,
+                                       const double* d_vort /* 3 x n_r complex, may be NULL if no vorticity bit is set */,
+                                       int n_nodes, int n_ext, int m, double k, double w_re, double w_im,
+                                       const double* d_x, int n_x, const double* d_y, int n_y, const double* d_z, int n_z,
+                                       const double* d_t, int n_t, uint32_t var_mask, double v_scale, float fill,
+                                       int flags, float* d_out);
 
 #ifdef __cplusplus
 }
