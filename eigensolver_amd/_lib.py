@@ -359,4 +359,8 @@ def _sig(lib):
         lib.es_cyl_complex_vorticity_amplitudes.argtypes = [vp, vp, vp, i, i, i, i, vp, vp]
         lib.es_cyl_complex_cartesian_synthesis.argtypes = [vp, vp, vp, vp, i, i, i, d, d, d, vp, i, vp, i, vp, i, vp, i,
                                                            C.c_uint32, d, C.c_float, i, vp]
+    # (21) dispersion curvature and group-speed extrema
+    if hasattr(lib, "es_shoot_root_curvature"):             # likewise
+        lib.es_shoot_root_curvature.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp]
+        lib.es_shoot_cg_extrema.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, d, vp, vp, vp, vp, vp, vp, vp, vp]
     return lib

@@ -3,10 +3,10 @@
 //              needs of its scalar type (fma, sqrt, exp, fabs, ldexp, fast_rcp, rcp, ke_pair, ie_pair_from_k, val).  ND = 2 is
 //              (value, d/d omega, d/dk), the Jet3 of es_shoot_root_slopes; ND = 1 is (value, d/d omega), what a Newton step in
 //              omega at fixed k needs -- k is then a constant jet.  Every operator is written once, over the component index.
-//   jet_march  the determinant's two sides at one (k, omega) pair in Jet<ND>: exterior, node entries by scalar loads
-//              (wave-uniform addresses, as mode_signature_kernel), the adjoint march with one reciprocal per RK4 step, the
-//              rescaling at the chunk ends and the boundary algebra.  Nothing is staged in LDS and there is no barrier: a lane
-//              may call it alone.
+//   jet_march  the determinant's two sides at one (k, omega) pair in Jet<ND> (jet_march_of: the same in any jet type, the
+//              second-order ones of es_jet2.hpp included): exterior, node entries by scalar loads (wave-uniform addresses,
+//              as mode_signature_kernel), the adjoint march with one reciprocal per RK4 step, the rescaling at the chunk
+//              ends and the boundary algebra.  Nothing is staged in LDS and there is no barrier: a lane may call it alone.
 //   * the node entries of make_entry depend on k only; the base fields themselves are wave-uniform, so make_entry delivers
 //     the k-dependent entries as jets and the others as plain doubles (its two output arrays)
 //   * the Bessel pairs of es_bessel.hpp are evaluated at the VALUES of their arguments; a pair (e^x K_n, e^x K_{n+1}) resp.
@@ -129,22 +129,29 @@ template <int ND> __device__ __forceinline__ bool jet_finite(const Jet<ND>& a) {
 
 // What jet_march returns: the two sides of the matching condition, the exterior status (ES_PT_OK / LEAKY / NONFINITE) and,
 // with TRACK, whether a watched term of the coefficients took both signs over the nodes (SignTrack::crossed).
-template <int ND> struct JetMatch {
-  Jet<ND> outer, inner;
+template <class J> struct JetMatchT {
+  J outer, inner;
   int status;
   bool crossed;
 };
+template <int ND> using JetMatch = JetMatchT<Jet<ND>>;
 
-// One (k, omega) pair: omega is variable 0 of the jets, k variable 1 (a constant for ND = 1).  TRACK: coef_pre follows the
-// signs of the watched terms through val(), as the value marches do.
-template <int FAM, int ND, bool TRACK>
-__device__ __forceinline__ JetMatch<ND> jet_march(const ShootDev& P, double kv, double wv) {
-  using J = Jet<ND>;
+// J's independent variable number `comp` at the value v_: what the march needs of a jet type besides its operators
+// (es_jet2.hpp gives the second-order Jet2<NV> the same)
+template <class J> struct JetVariable;
+template <int ND> struct JetVariable<Jet<ND>> {
+  static __device__ __forceinline__ Jet<ND> make(double v_, int comp) { return jet_variable<ND>(v_, comp); }
+};
+
+// One (k, omega) pair in the jet type J: omega is variable 0 of the jets, k variable 1 (a constant for a jet of one
+// variable).  TRACK: coef_pre follows the signs of the watched terms through val(), as the value marches do.
+template <int FAM, class J, bool TRACK>
+__device__ __forceinline__ JetMatchT<J> jet_march_of(const ShootDev& P, double kv, double wv) {
   using namespace es_shoot_shared;
   constexpr int NB = FamTraits<FAM>::NB;
   constexpr int NE = FamTraits<FAM>::NE;
-  const J w = jet_variable<ND>(wv, 0);
-  const KScalT<J> s = make_kscal(P, jet_variable<ND>(kv, 1));
+  const J w = JetVariable<J>::make(wv, 0);
+  const KScalT<J> s = make_kscal(P, JetVariable<J>::make(kv, 1));
   const int nsteps = P.n_nodes - 1;
   const double h = P.h, h2 = 0.5 * P.h, h6 = P.h / 6.0, h3 = P.h / 3.0;
   const ExteriorLiteT<J> X = exterior_lite<FAM>(P, s.k, w, w);
@@ -183,10 +190,15 @@ __device__ __forceinline__ JetMatch<ND> jet_march(const ShootDev& P, double kv, 
   load_base<FAM>(P, 0, b);
   make_entry<FAM>(b, s, e1, c1);                               // the boundary node
   const MismatchT<J> M = boundary_algebra<FAM>(P, s, w, X, zp, zq, e1);
-  JetMatch<ND> R;
+  JetMatchT<J> R;
   R.outer = M.outer;
   R.inner = M.inner;
   R.status = X.status;
   R.crossed = TRACK ? trk.crossed() : false;
   return R;
+}
+
+template <int FAM, int ND, bool TRACK>
+__device__ __forceinline__ JetMatch<ND> jet_march(const ShootDev& P, double kv, double wv) {
+  return jet_march_of<FAM, Jet<ND>, TRACK>(P, kv, wv);
 }

@@ -147,6 +147,39 @@ def hermite_branch(ks, omegas, cg):
     return f
 
 
+def hermite_branch_quintic(ks, omegas, cg, curv):
+    """hermite_branch with the curvature known as well: omega(k) of one branch as the piecewise-quintic Hermite interpolant
+    through the roots (ks strictly increasing) with the slopes cg = d omega / dk and the second derivatives
+    curv = d2 omega / dk2 (ShootProblem.root_curvature).  Returns f(k, nu=0): omega (nu = 0), d omega / dk (nu = 1) or
+    d2 omega / dk2 (nu = 2) at scalar or array k, all three continuous at the knots; outside [ks[0], ks[-1]] the quintic of
+    the end interval is continued."""
+    x, y, d, c = (np.asarray(a, dtype=np.float64) for a in (ks, omegas, cg, curv))
+    if not (x.ndim == 1 and x.shape == y.shape == d.shape == c.shape and len(x) >= 2):
+        raise ValueError("ks, omegas, cg, curv must be 1-D arrays of one length >= 2")
+    if not np.all(np.diff(x) > 0):
+        raise ValueError("ks must be strictly increasing")
+    h = np.diff(x)
+    # per interval, in t = (k - k_j) / h: a0 + a1 t + ... + a5 t^5 with the six end conditions
+    dy, d0, d1, c0, c1 = y[1:] - y[:-1], h * d[:-1], h * d[1:], h * h * c[:-1], h * h * c[1:]
+    a = np.array([y[:-1], d0, 0.5 * c0,
+                  10.0 * dy - 6.0 * d0 - 4.0 * d1 - 0.5 * (3.0 * c0 - c1),
+                  -15.0 * dy + 8.0 * d0 + 7.0 * d1 + 0.5 * (3.0 * c0 - 2.0 * c1),
+                  6.0 * dy - 3.0 * d0 - 3.0 * d1 - 0.5 * (c0 - c1)])
+
+    def f(k, nu=0):
+        if nu not in (0, 1, 2):
+            raise ValueError("nu must be 0, 1 or 2")
+        k = np.asarray(k, dtype=np.float64)
+        j = np.clip(np.searchsorted(x, k, side="right") - 1, 0, len(x) - 2)
+        t = (k - x[j]) / h[j]
+        out = np.zeros_like(t)
+        for p in range(5, nu - 1, -1):                          # Horner on the nu-th derivative in t
+            fac = float(np.prod(np.arange(p - nu + 1, p + 1))) if nu else 1.0
+            out = out * t + fac * a[p][j]
+        return out / h[j] ** nu
+    return f
+
+
 def _hermite_complex_arrays(ks, omegas, dwdk):
     x = np.asarray(ks, dtype=np.float64)
     y, d = np.asarray(omegas, dtype=np.complex128), np.asarray(dwdk, dtype=np.complex128)

@@ -60,6 +60,42 @@ class RootSlopes(NamedTuple):
         return -self.d / self.d_w
 
 
+class RootCurvature(NamedTuple):
+    """es_shoot_root_curvature: RootSlopes with the exact second partial derivatives, CUDA tensors.  outer, inner are [6, n]
+    (value, d/d omega, d/dk, d2/d omega2, d2/d omega dk, d2/dk2); the other fields [n] are D = outer - inner and its
+    derivatives.  A pair that is not PT_OK, or whose outputs are not finite, carries NaN throughout."""
+    outer: object
+    inner: object
+    D: object
+    D_w: object
+    D_k: object
+    D_ww: object
+    D_wk: object
+    D_kk: object
+    status: object            # uint8: PT_* of the exterior
+
+    @property
+    def group_velocity(self):
+        """d omega / dk along the branch through each pair: -D_k / D_w."""
+        return -self.D_k / self.D_w
+
+    @property
+    def curvature(self):
+        """d2 omega / dk2 = d c_g / dk along the branch through each pair: -(D_kk + 2 D_wk c_g + D_ww c_g^2) / D_w."""
+        cg = self.group_velocity
+        return -(self.D_kk + 2.0 * self.D_wk * cg + self.D_ww * cg * cg) / self.D_w
+
+    @property
+    def newton_dw(self):
+        """The Newton correction -D / D_w."""
+        return -self.D / self.D_w
+
+    @property
+    def halley_dw(self):
+        """The Halley correction -2 D D_w / (2 D_w^2 - D D_ww): Newton's with the curvature of D in omega taken along."""
+        return -2.0 * self.D * self.D_w / (2.0 * self.D_w * self.D_w - self.D * self.D_ww)
+
+
 class TracedBranches(NamedTuple):
     """ShootProblem.trace_branches: `branches` {label: dict of CUDA tensors k, w, dwdk, resid, iters, flag, status, predicted,
     max_shift}, views into the tensors of the one Newton launch; `skipped` the labels that were not traced (a single row,
@@ -675,6 +711,87 @@ class ShootProblem:
                 same = (sig.nodes_value == dlv.to(torch.int32)) & (sig.nodes_flux == dlf.to(torch.int32))
                 out["flag"] = torch.where(same, out["flag"], torch.zeros_like(out["flag"]))
         return TracedBranches({label: {key: v[a:b] for key, v in out.items()} for label, (a, b) in spans.items()}, skipped)
+
+    # ---- curvature and group-speed extrema (C ABI section 21) ---------------------------------------------------------
+    @staticmethod
+    def _check_count(count):
+        import torch
+        if count is not None:
+            assert count.is_cuda and count.numel() >= 1 and count.dtype == torch.int32
+
+    def root_curvature(self, k, w, count=None):
+        """es_shoot_root_curvature at the (k, omega) pairs: root_slopes with the exact second derivatives of both sides in
+        omega and k (a second-order forward-mode march, no difference step) -> RootCurvature.  count as in mode_signature:
+        entries past min(count, n) are left as allocated.  Nothing is read back."""
+        import torch
+        dk, dw = self._dev(k).reshape(-1), self._dev(w).reshape(-1)
+        n = dk.numel()
+        assert dw.numel() == n
+        self._check_count(count)
+        outer = torch.empty((6, n), dtype=torch.float64, device=dk.device)
+        inner = torch.empty((6, n), dtype=torch.float64, device=dk.device)
+        st = torch.empty(n, dtype=torch.uint8, device=dk.device)
+        rc = self.ctx.lib.es_shoot_root_curvature(self.ctx.handle, self.handle, _lib.ptr(dk), _lib.ptr(dw), n,
+                                                  _lib.ptr(count) if count is not None else None, _lib.ptr(outer),
+                                                  _lib.ptr(inner), _lib.ptr(st))
+        _lib.check(self.ctx.handle, rc)
+        diff = outer - inner
+        return RootCurvature(outer, inner, *diff, st)
+
+    def cg_extrema(self, k_lo, w_lo, k_hi, w_hi, max_iter=40, tol_percent=None, count=None):
+        """es_shoot_cg_extrema: per entry a bracket (k_lo, w_lo), (k_hi, w_hi) on one branch, k_lo < k_hi, both roots or
+        near-roots; the wavenumber between them at which d2 omega / dk2 changes sign -- an extremum of the group speed --
+        by regula falsi (Illinois) on the exact curvature, every point polished by Newton in omega.  Dict of CUDA tensors
+        k, w, cg, q (the curvature there), resid (percent), iters, flag (int32) and status (uint8).  flag = 1: the curvature
+        changed sign over the bracket, every polish succeeded, the point is PT_OK and resid < tol_percent (default 1e-3);
+        without a sign change the end with the smaller |q| is reported, flag 0.  count as in mode_signature.  Nothing is
+        read back."""
+        import torch
+        kl, wl, kh, wh = (self._dev(a).reshape(-1) for a in (k_lo, w_lo, k_hi, w_hi))
+        n, dev = kl.numel(), kl.device
+        assert wl.numel() == n and kh.numel() == n and wh.numel() == n
+        self._check_count(count)
+        k, w, cg, q, resid = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(5))
+        iters, flag = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        st = torch.empty(n, dtype=torch.uint8, device=dev)
+        rc = self.ctx.lib.es_shoot_cg_extrema(self.ctx.handle, self.handle, _lib.ptr(kl), _lib.ptr(wl), _lib.ptr(kh),
+                                              _lib.ptr(wh), n, _lib.ptr(count) if count is not None else None, int(max_iter),
+                                              1e-3 if tol_percent is None else float(tol_percent), _lib.ptr(k), _lib.ptr(w),
+                                              _lib.ptr(cg), _lib.ptr(q), _lib.ptr(resid), _lib.ptr(iters), _lib.ptr(flag),
+                                              _lib.ptr(st))
+        _lib.check(self.ctx.handle, rc)
+        return dict(k=k, w=w, cg=cg, q=q, resid=resid, iters=iters, flag=flag, status=st)
+
+    def group_speed_extrema(self, branch, max_iter=40, tol_percent=None):
+        """The extrema of the group speed along one traced branch: `branch` is an entry of TracedBranches.branches, or any
+        dict of CUDA tensors k (increasing), w and flag.  (1) root_curvature at the flagged points, (2) the neighbouring
+        flagged points between which the curvature changes sign, selected and moved to the front on the device, (3) one
+        cg_extrema call over them.  Returns the dict of cg_extrema, its tensors as long as the branch less one, with
+        `count` (int32 CUDA tensor of one element): the number of extrema, which lie in the leading entries in the order of
+        k; the entries past it are left as allocated.  A change of sign is strict, as in cg_extrema: a traced point whose
+        curvature is exactly zero is an extremum by itself and is not reported (root_curvature at the branch shows it).
+        k, w and flag may be tensors on any device or arrays.  Nothing is read back."""
+        import torch
+        with torch.cuda.stream(self.ctx.torch_stream):
+            k, w = self._dev(branch["k"]).reshape(-1), self._dev(branch["w"]).reshape(-1)
+            n = k.numel()
+            if n < 2 or w.numel() != n:
+                raise ValueError("group_speed_extrema needs a branch of at least two points")
+            ok = self._dev(branch["flag"]).reshape(-1) != 0
+            if ok.numel() != n:
+                raise ValueError("group_speed_extrema needs one flag per point of the branch")
+            order = torch.argsort((~ok).to(torch.int8), stable=True)         # the flagged points first, in their order
+            n_ok = ok.sum().to(torch.int32).reshape(1)
+            k, w = k[order].contiguous(), w[order].contiguous()
+            q = self.root_curvature(k, w, count=n_ok).curvature
+            pair = torch.arange(n - 1, device=k.device) < n_ok - 1          # both points of the pair flagged
+            change = pair & (((q[:-1] < 0) & (q[1:] > 0)) | ((q[:-1] > 0) & (q[1:] < 0)))
+            sel = torch.argsort((~change).to(torch.int8), stable=True)
+            n_change = change.sum().to(torch.int32).reshape(1)
+            out = self.cg_extrema(k[:-1][sel], w[:-1][sel], k[1:][sel], w[1:][sel], max_iter=max_iter,
+                                  tol_percent=tol_percent, count=n_change)
+            out["count"] = n_change
+            return out
 
     def _require_positive_cylinder(self):
         if not isinstance(self.eq, eqm._CylinderBase):

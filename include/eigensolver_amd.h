@@ -1321,6 +1321,51 @@ int es_cyl_complex_cartesian_synthesis(es_context* ctx, const double* d_radius, 
                                        const double* d_t, int n_t, uint32_t var_mask, double v_scale, float fill,
                                        int flags, float* d_out);
 
+/* ======================================================================================================
+ * (21) Dispersion curvature: the second partial derivatives of the boundary determinant and the extrema of the group speed.
+ *     With D, D_w, D_k of section 11 and D_ww, D_wk, D_kk, along the branch through a root
+ *       the curvature              q = d2 omega / dk2 = d c_g / dk = -(D_kk + 2 D_wk c_g + D_ww c_g^2) / D_w,
+ *                                  the group-velocity dispersion of a packet at k; it changes sign at an extremum of c_g
+ *                                  (the Airy phase of an impulsively generated wave train),
+ *       the Halley correction      d omega = -2 D D_w / (2 D_w^2 - D D_ww).
+ *
+ *     es_shoot_root_curvature: section 11's evaluation carried in six-component second-order jets -- exact to rounding, no
+ *     step to choose.  Everything of es_shoot_root_slopes holds: one pair per lane, d_count, entries beyond the count left
+ *     alone, any output pointer may be NULL, the asynchrony, n == 0, the argument errors.
+ *       d_outer / d_inner [6][n]: rows 0-2 as section 11 (the same arithmetic), row 3 d2/d omega2, row 4 d2/d omega dk,
+ *         row 5 d2/dk2 of the two sides.  The rows are n apart.
+ *       d_status [n]: as section 11.  A pair whose exterior is not ES_PT_OK, or one of whose twelve outputs is not finite,
+ *         gets NaN in all twelve.
+ *
+ *     es_shoot_cg_extrema: per lane a bracket on ONE branch, (k_lo, w_lo) and (k_hi, w_hi) with k_lo < k_hi, both roots or
+ *     near-roots (e.g. neighbouring points of a Newton trace); the k at which the curvature changes sign between them.
+ *       A point (k, w) is polished by Newton in omega at fixed k -- at most 8 steps, until |step| <= 1e-14 |omega|, failing
+ *       on what fails a step of es_shoot_newton (no step cap) -- and evaluated once at second order: c_g, q, the status and
+ *       the residual (percent) of es_shoot_eval_points there.
+ *       Both ends are treated so.  If q_lo and q_hi do not differ in sign (a zero or a NaN differs from nothing) the end with
+ *       the smaller |q| is reported (a finite one before a non-finite one), flag 0, iters 0.  Otherwise regula falsi with the
+ *       Illinois modification on q(k): k_new = k_hi - f_hi (k_hi - k_lo) / (f_hi - f_lo) (the midpoint should rounding put it
+ *       outside the open bracket), omega from the nearer end's Taylor prediction w + c_g dk + q dk^2 / 2, polished and
+ *       evaluated as above; the new point replaces the end whose q has its sign, and where the same end is replaced twice
+ *       running the ordinate f of the other end is halved.  Stops at q = 0, at k_hi - k_lo <= 1e-12 |k_new|, after
+ *       max_iter iterates, or at an iterate whose polish failed or whose q is not finite.  The last iterate is reported.
+ *       Every tolerance is relative: nothing ties the rule to a unit system.
+ *       d_k, d_w, d_cg, d_q, d_resid, d_iters (iterates taken), d_flag [n]; d_status [n] (may be NULL).  flag = 1: the sign
+ *       changed, every polish succeeded, the reported point is ES_PT_OK and resid < tol_percent.  A reported point without
+ *       a value (leaky, non-finite) carries NaN in c_g, q and resid.
+ *       ES_ERR_INVALID_ARG: a null problem, n < 0, max_iter < 0, tol_percent <= 0, a required pointer null with n > 0.
+ *     Not offered: complex frequencies (sections 12, 15, 18), the closed-form uniform cylinder (section 4), third derivatives.
+ * ====================================================================================================== */
+int es_shoot_root_curvature(es_context* ctx, const es_problem* prob, const double* d_k, const double* d_w, int n,
+                            const int32_t* d_count /* may be NULL */,
+                            double* d_outer /* [6][n]: value, d/dw, d/dk, d2/dw2, d2/dwdk, d2/dk2 */,
+                            double* d_inner /* [6][n] */, uint8_t* d_status);
+
+int es_shoot_cg_extrema(es_context* ctx, const es_problem* prob, const double* d_k_lo, const double* d_w_lo,
+                        const double* d_k_hi, const double* d_w_hi, int n, const int32_t* d_count /* may be NULL */,
+                        int max_iter, double tol_percent, double* d_k, double* d_w, double* d_cg, double* d_q,
+                        double* d_resid, int32_t* d_iters, int32_t* d_flag, uint8_t* d_status /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
