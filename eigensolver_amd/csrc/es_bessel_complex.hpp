@@ -47,6 +47,8 @@
 namespace esb {
 
 // ---- the complex scalar: every operator the formula text of es_shoot_device.hpp asks of its scalar type ---------------------
+// esb::cz is the library's only complex scalar and esb::CJet<ND> (es_cjet.hpp) its only complex jet: the slab, the cylinder,
+// the Bessel routines and the field kernels all compute with these two, so a primitive is measured, and corrected, in one place.
 struct cz {
   double re, im;
   cz() = default;
@@ -95,6 +97,17 @@ ES_HD cz cz_sqrt(cz z) {
 ES_HD cz cz_exp(cz z) {
   const double e = exp(z.re);
   return cz(e * cos(z.im), e * sin(z.im));
+}
+// The same exponential with sine and cosine from one sincos call: the flow slab's (es_complex_shared.hpp, es_complex.hip).
+// Two forms for the registers, not for the values: with cos and sin apart the slab kernels take up to 12 more vector registers
+// and cx_refine_kernel spills; with sincos here and in the cylinder's exterior cylc_refine_kernel<FAM_CYLT> spills four vector
+// registers, which it must not (tests/test_cyl_complex_codeobj.py).  On an MI355X the two gave the same bits in every output
+// of tools/compare_complex_builds.py; only the es_complex_* entry points use this form, and no formula uses both.
+ES_HD cz cz_exp_sincos(cz z) {
+  const double e = exp(z.re);
+  double s, c;
+  sincos(z.im, &s, &c);
+  return cz(e * c, e * s);
 }
 // principal logarithm
 ES_HD cz cz_log(cz z) { return cz(log(hypot(z.re, z.im)), atan2(z.im, z.re)); }

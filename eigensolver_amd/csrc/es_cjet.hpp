@@ -1,15 +1,18 @@
-// Forward-mode jets of the complex cylinder path (include/eigensolver_amd.h section 15).
+// Forward-mode jets of the complex-frequency paths: the cylinder (include/eigensolver_amd.h sections 15 and 18) and the flow
+// slab (section 12).  esb::cz (es_bessel_complex.hpp) and esb::CJet are the library's only complex scalar and complex jet.
 //   CJet<ND>   an esb::cz value with ND esb::cz derivative components, and the operators and overloads the FAM_CYL0 formula
-//              text of es_shoot_device.hpp and the exterior of es_cyl_complex_shared.hpp need of their scalar type (fma, rcp,
-//              sqrt, exp, val, lift, cke_pair, cie_pair_from_k, all_finite).  ND = 2 is (value, d/d omega, d/dk); ND = 1 is
-//              (value, d/d omega), what a Newton step in omega at fixed k needs -- k is then a constant.  Every operator is
-//              written once, over the component index, as Jet<ND> of es_jet.hpp is.
+//              text of es_shoot_device.hpp, the exterior of es_cyl_complex_shared.hpp and the slab's text of
+//              es_complex_shared.hpp need of their scalar type (fma, rcp, sqrt, exp, val, lift, cke_pair, cie_pair_from_k,
+//              all_finite).  ND = 2 is (value, d/d omega, d/dk); ND = 1 is (value, d/d omega), what a Newton step in omega
+//              at fixed k needs -- k is then a constant.  Every operator is written once, over the component index, as
+//              Jet<ND> of es_jet.hpp is.
 //   * all derivatives are holomorphic in omega; k is real and is differentiated as a real parameter, so d/dk of a
 //     holomorphic expression is again one complex number per component
 //   * the value component of every operation is the one esb::cz operation the plain complex path takes, and the library is
 //     built without contraction: component 0 of a jet evaluation is the cz evaluation
 //   * the Bessel pairs of es_bessel_complex.hpp are evaluated at the VALUES of their arguments; a pair carries its own
 //     argument derivative (lift) by the identities of es_jet.hpp, which hold unchanged at complex argument
+//   RealK      a real function of k with its k-derivative, the wavenumber type of the slab's evaluation at CJet<2>; real_of_k
 // Builds for the host as well (ES_HD), as es_bessel_complex.hpp does.
 #pragma once
 #include "es_bessel_complex.hpp"
@@ -21,6 +24,7 @@ ES_HD cz sqrt(cz a) { return cz_sqrt(a); }
 ES_HD cz exp(cz a) { return cz_exp(a); }
 ES_HD cz value_of(cz a) { return a; }
 ES_HD bool all_finite(cz a) { return cz_finite(a); }
+ES_HD cz lift(cz f, cz, cz) { return f; }                      // f(x) of a plain value: no derivative to carry
 
 // ---- the jet -----------------------------------------------------------------------------------------------------------------
 template <int ND> struct CJet {
@@ -103,6 +107,47 @@ ES_CJET exp(const CJet<ND>& a) {
 ES_CJET lift(cz f, cz df, const CJet<ND>& x) { return cjet_of<ND>(f, [&](int c) { return df * x.d[c]; }); }
 #undef ES_CJET
 #undef ES_CJET_S
+
+// ---- real functions of the wavenumber, for the flow slab's text (es_complex_shared.hpp) ---------------------------------------
+// RealK: a real function of k alone -- k, k^2 c^2, k U' -- with its k-derivative, the wavenumber type K of an evaluation at
+// CJet<2> = (value, d/d omega, d/dk).  Two doubles and the few operators against CJet<2> below: such a quantity has no
+// imaginary part and no d/d omega, and carrying it as a CJet<2> multiplied those zeros through every node (the slab's slopes
+// kernel took 14 % longer).  CJet<2>(a) is the explicit widening, for the quotient a / z.
+struct RealK {
+  double v, dk;
+  ES_HDM explicit operator CJet<2>() const {
+    CJet<2> r{cz(v)};
+    r.d[1] = cz(dk);
+    return r;
+  }
+};
+ES_HD double val(RealK a) { return a.v; }
+ES_HD RealK operator*(RealK a, double b) { return RealK{a.v * b, a.dk * b}; }
+ES_HD RealK operator*(double a, RealK b) { return RealK{a * b.v, a * b.dk}; }
+ES_HD CJet<2> operator-(RealK a, const CJet<2>& b) {
+  CJet<2> r = -b;
+  r.v = a.v - b.v;
+  r.d[1] = a.dk - b.d[1];
+  return r;
+}
+ES_HD CJet<2> operator-(const CJet<2>& a, RealK b) {
+  CJet<2> r = a;
+  r.v = a.v - b.v;
+  r.d[1] = a.d[1] - b.dk;
+  return r;
+}
+ES_HD CJet<2> operator*(RealK a, const CJet<2>& b) {
+  CJet<2> r;
+  r.v = a.v * b.v;
+  r.d[0] = a.v * b.d[0];
+  r.d[1] = a.v * b.d[1] + a.dk * b.v;
+  return r;
+}
+// The real function of k with value v and k-derivative dv as the wavenumber type of `k` carries it: the value where k is a
+// constant of the differentiation (double), the pair where it is the variable (RealK).  The formula text hands over such
+// derivatives as it has always rounded them (R / k, not -R (1 / k)): no jet arithmetic is asked to derive them again.
+ES_HD double real_of_k(double, double v, double) { return v; }
+ES_HD RealK real_of_k(RealK, double v, double dv) { return RealK{v, dv}; }
 
 // d/dz [e^z K_n] = e^z K_n - e^z K_{n+1} + (n/z) e^z K_n ;  d/dz [e^z K_{n+1}] = e^z K_{n+1} - e^z K_n - ((n+1)/z) e^z K_{n+1}
 template <int ND> ES_HD void cke_pair(int n, const CJet<ND>& z, CJet<ND>& K, CJet<ND>& K1) {

@@ -1,22 +1,21 @@
 // K6: complex-frequency determinant of the flow slab, winding-number cell detection and complex secant refinement,
 // eigenfunctions at given complex (k, omega).
 // See include/eigensolver_amd.h section (6) for the reference lines this replaces and oracle/slab_complex.py for the
-// CPU restatement.  The formulas (coefficients, exterior, adjoint march, boundary) are the W = 1 instances of
-// es_complex_shared.hpp, the text es_complex_slopes.hip differentiates; here are the kernels around them: one (k, omega)
-// point per lane, the forward march of the eigenfunction, the winding-number flags and the secant refinement.  The search is
-// shared with the cylinder (es_cyl_complex.hip) through es_complex_roots.hpp: the flag and emit kernels live here behind
-// cx_candidates, the refinement loop and the host side of a find_roots call are the header's.
+// CPU restatement.  The formulas (coefficients, exterior, adjoint march, boundary) are the text of es_complex_shared.hpp at
+// the plain complex scalar esb::cz, the text es_complex_slopes.hip runs over jets; here are the kernels around them: one
+// (k, omega) point per lane, the forward march of the eigenfunction, the winding-number flags and the secant refinement.
+// The search is shared with the cylinder (es_cyl_complex.hip) through es_complex_roots.hpp: the flag and emit kernels live
+// here behind cx_candidates, the refinement loop and the host side of a find_roots call are the header's.
 #include "es_complex_roots.hpp"
 
 namespace {
 using namespace es_complex_shared;
-using cv = cj<1>;                    // the plain complex value as the formulas take it
 
 // D_c = outer - inner at one point, NaN unless st == ES_PT_OK.  Every lane of the workgroup must call this.
-__device__ __forceinline__ void cx_shoot_point(const ShootDev& P, int variant, double k, cx w, cx& D, double& rel,
+__device__ __forceinline__ void cx_shoot_point(const ShootDev& P, int variant, double k, cz w, cz& D, double& rel,
                                                uint8_t& st, double* __restrict__ sb) {
-  const CxMatch<1> B = cx_eval<1>(P, variant, k, w, sb);
-  D = (B.st == ES_PT_OK) ? B.outer.c[0] - B.inner.c[0] : cx{NAN, NAN};
+  const CxMatch<cz> B = cx_eval(P, variant, k, w, sb);
+  D = (B.st == ES_PT_OK) ? B.outer - B.inner : cz(NAN, NAN);
   rel = B.rel; st = B.st;
 }
 
@@ -30,7 +29,7 @@ __global__ __launch_bounds__(256) void cx_eval_kernel(ShootDev P, int variant, c
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;
   double k = 1.0;
-  cx w = cx{1.0, 0.1};
+  cz w = cz(1.0, 0.1);
   if (in) {
     if (n_re > 0) {
       const long row = i / ((long)n_re * n_im);
@@ -40,10 +39,10 @@ __global__ __launch_bounds__(256) void cx_eval_kernel(ShootDev P, int variant, c
       w = cx_pick_w(w_mode, k, wre[ire], wim[iim]);
     } else {
       k = kv[i];
-      w = cx{wre[i], wim[i]};
+      w = cz(wre[i], wim[i]);
     }
   }
-  cx D; double rel; uint8_t st;
+  cz D; double rel; uint8_t st;
   cx_shoot_point(P, variant, k, w, D, rel, st, sb);
   if (in) {
     Dre[i] = D.re;
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(256) void cx_eval_kernel(ShootDev P, int variant, c
 
 // ---- eigenfunctions at given (k, omega) -----------------------------------------------------------------------------
 // rhs of the forward system: A y with A = [[0, 1], [a21, a22]]
-__device__ __forceinline__ void cx_rhs_fwd(const CxNode<1>& A, const cv& u, const cv& v, cv& ku, cv& kv) {
+__device__ __forceinline__ void cx_rhs_fwd(const CxNode<cz>& A, const cz& u, const cz& v, cz& ku, cz& kv) {
   ku = v;
   kv = A.a21 * u + A.a22 * v;
 }
@@ -73,46 +72,46 @@ __global__ __launch_bounds__(64) void cx_eigen_interior_kernel(ShootDev P, int v
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;
   const double k = in ? kv[i] : 1.0;
-  const cx w = in ? cx{wre[i], wim[i]} : cx{1.0, 0.1};
-  const CxConsts C = cx_consts(P, variant, k);
-  const CxOutside<1> X = cx_exterior<1>(P, C, k, w);
+  const cz w = in ? cz(wre[i], wim[i]) : cz(1.0, 0.1);
+  const CxConsts<double> C = cx_consts(P, variant, k);
+  const CxOutside<cz> X = cx_exterior(P, C, w);
   // (1) the row of the transfer matrix picked by the far-end condition -> boundary state and status
-  cv zp, zq;
+  cz zp, zq;
   double Ub, dUb;
-  cx_adjoint<1>(P, C, w, sb, zp, zq, Ub, dUb);
-  const CxMatch<1> B = cx_boundary<1>(P, C, X, w, zp, zq, Ub, dUb);
+  cx_adjoint(P, C, w, sb, zp, zq, Ub, dUb);
+  const CxMatch<cz> B = cx_boundary(P, C, X, w, zp, zq, Ub, dUb);
   const bool ok = B.st == ES_PT_OK;
   if (in) stout[i] = B.st;
   // (2) forward march from the boundary, writing every node
-  cv u = B.Vb, v = B.sv;
+  cz u = B.Vb, v = B.sv;
   auto store = [&](int node, double U, double dU) {
     if (!in) return;
-    const cv Om = doppler<1>(w, k, U);
-    const cx pt = cx_total_pressure<1>(P, C, Om, Om * Om, dU, u, v).c[0];
+    const cz Om = w - k * U;
+    const cz pt = cx_total_pressure(P, C, Om, Om * Om, dU, u, v);
     const size_t o = 2 * ((size_t)i * P.n_nodes + node);
-    val[o] = ok ? u.c[0].re : NAN;
-    val[o + 1] = ok ? u.c[0].im : NAN;
+    val[o] = ok ? u.re : NAN;
+    val[o + 1] = ok ? u.im : NAN;
     flux[o] = ok ? pt.re : NAN;
     flux[o + 1] = ok ? pt.im : NAN;
   };
   const int nsteps = P.n_nodes - 1;
   const double h = P.h, h2 = 0.5 * P.h, h6 = P.h / 6.0, h3 = P.h / 3.0;
-  CxNode<1> A0{jconst<1>(0.0), jconst<1>(0.0)};
+  CxNode<cz> A0{cz(0.0), cz(0.0)};
   const int nchunks = (nsteps + CH - 1) / CH;
   for (int c = 0; c < nchunks; ++c) {
     const int c0 = c * CH;
     const int nst = (nsteps - c0 < CH) ? (nsteps - c0) : CH;
     cx_stage_chunk(P, c0, nst, sb);
     if (c == 0) {
-      A0 = cx_coef<1>(C, w, sb[SF_U], sb[SF_DU], sb[SF_DDU]);
+      A0 = cx_coef(C, w, sb[SF_U], sb[SF_DU], sb[SF_DDU]);
       store(0, sb[SF_U], sb[SF_DU]);
     }
     for (int j = 0; j < nst; ++j) {
       const double* bm = sb + (2 * j + 1) * NB;
       const double* b1 = sb + (2 * j + 2) * NB;
-      const CxNode<1> Am = cx_coef<1>(C, w, bm[SF_U], bm[SF_DU], bm[SF_DDU]);
-      const CxNode<1> A1 = cx_coef<1>(C, w, b1[SF_U], b1[SF_DU], b1[SF_DDU]);
-      cv k1u, k1v, k2u, k2v, k3u, k3v, k4u, k4v;
+      const CxNode<cz> Am = cx_coef(C, w, bm[SF_U], bm[SF_DU], bm[SF_DDU]);
+      const CxNode<cz> A1 = cx_coef(C, w, b1[SF_U], b1[SF_DU], b1[SF_DDU]);
+      cz k1u, k1v, k2u, k2v, k3u, k3v, k4u, k4v;
       cx_rhs_fwd(A0, u, v, k1u, k1v);
       cx_rhs_fwd(Am, u + h2 * k1u, v + h2 * k1v, k2u, k2v);
       cx_rhs_fwd(Am, u + h2 * k2u, v + h2 * k2v, k3u, k3v);
@@ -136,20 +135,20 @@ __global__ __launch_bounds__(256) void cx_eigen_exterior_kernel(ShootDev P, int 
   if (t >= (long)n * n_ext) return;
   const int i = (int)(t / n_ext), j = (int)(t - (long)i * n_ext);
   const double k = kv[i];
-  const cx w = cx{wre[i], wim[i]};
-  const CxOutside<1> X = cx_exterior<1>(P, cx_consts(P, variant, k), k, w);
-  const cx mu = X.mu.c[0], gp = X.gp.c[0], gm = X.gm.c[0];
+  const cz w = cz(wre[i], wim[i]);
+  const CxOutside<cz> X = cx_exterior(P, cx_consts(P, variant, k), w);
+  const cz mu = X.mu, gp = X.gp, gm = X.gm;
   // np.linspace(-R, -1, n_ext)[j]
   const double step = (-1.0 + X.R) / (double)(n_ext - 1);
   const double x = (j == n_ext - 1) ? -1.0 : -X.R + (double)j * step;
   const double ax = fabs(x);
-  cx v = cx{NAN, NAN}, f = cx{NAN, NAN};
+  cz v = cz(NAN, NAN), f = cz(NAN, NAN);
   if (st[i] == ES_PT_OK) {
-    const cx E2x = cexp_((-2.0 * (X.R - ax)) * mu);
-    const cx dec = cexp_((-(ax - 1.0)) * mu);
-    const cx den = gp + X.E2.c[0] * gm;
+    const cz E2x = esb::cz_exp_sincos((-2.0 * (X.R - ax)) * mu);
+    const cz dec = esb::cz_exp_sincos((-(ax - 1.0)) * mu);
+    const cz den = gp + X.E2 * gm;
     v = dec * ((gp + E2x * gm) / den);
-    f = X.p_e.c[0] * (mu * (dec * ((gp - E2x * gm) / den)));                           // left_P = p_e_const * Vx'
+    f = X.p_e * (mu * (dec * ((gp - E2x * gm) / den)));                           // left_P = p_e_const * Vx'
   }
   xs[t] = x;
   val[2 * t] = v.re;
@@ -203,8 +202,8 @@ __global__ __launch_bounds__(256) void cx_emit_kernel(const double* __restrict__
   const long r = c - row * per_row;
   const int iim = (int)(r / n_re), ire = (int)(r - (long)iim * n_re);
   const double k = kv[row];
-  const cx a = cx_pick_w(w_mode, k, wre[ire], wim[iim]);
-  const cx b = cx_pick_w(w_mode, k, wre[ire + 1], wim[iim + 1]);
+  const cz a = cx_pick_w(w_mode, k, wre[ire], wim[iim]);
+  const cz b = cx_pick_w(w_mode, k, wre[ire + 1], wim[iim + 1]);
   tab.d_k[pos] = k;
   tab.d_row[pos] = (int32_t)row;
   tab.d_w_re[pos] = 0.5 * (a.re + b.re);                   // cell centre: start of the refinement
@@ -220,7 +219,7 @@ __global__ __launch_bounds__(64) void cx_refine_kernel(ShootDev P, int variant, 
                                                        double tol_percent) {
   __shared__ double sb[CX_LDS_DOUBLES];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  cx_refine_candidate([&](double k, cx w, cx& f, double& rel, uint8_t& st) { cx_shoot_point(P, variant, k, w, f, rel, st, sb); },
+  cx_refine_candidate([&](double k, cz w, cz& f, double& rel, uint8_t& st) { cx_shoot_point(P, variant, k, w, f, rel, st, sb); },
                       tab, half_re, half_im, i, n, n_iter, tol_percent);
 }
 

@@ -9,8 +9,8 @@
 
 namespace es_complex_shared {
 
-__device__ __forceinline__ cx cx_pick_w(int w_mode, double k, double wre, double wim) {
-  return (w_mode == ES_W_PHASE_SPEED) ? cx{k * wre, k * wim} : cx{wre, wim};
+__device__ __forceinline__ cz cx_pick_w(int w_mode, double k, double wre, double wim) {
+  return (w_mode == ES_W_PHASE_SPEED) ? cz(k * wre, k * wim) : cz(wre, wim);
 }
 
 // Flags the cells around which D_c winds, scans, and writes k, row and the cell centre of the first min(total, capacity)
@@ -29,25 +29,25 @@ __device__ __forceinline__ void cx_refine_candidate(Eval eval, es_complex_root_t
                                                     double tol_percent) {
   const bool in = i < n;
   const double k = in ? tab.d_k[i] : 1.0;
-  const cx centre = in ? cx{tab.d_w_re[i], tab.d_w_im[i]} : cx{1.0, 0.1};
-  const cx half = in ? cx{half_re[i], half_im[i]} : cx{0.1, 0.1};
-  cx w0 = centre, w1 = centre + cx{0.5 * half.re, 0.5 * half.im};
-  cx f0, f1; double rel0, rel1; uint8_t s0, s1;
+  const cz centre = in ? cz(tab.d_w_re[i], tab.d_w_im[i]) : cz(1.0, 0.1);
+  const cz half = in ? cz(half_re[i], half_im[i]) : cz(0.1, 0.1);
+  cz w0 = centre, w1 = centre + 0.5 * half;
+  cz f0, f1; double rel0, rel1; uint8_t s0, s1;
   eval(k, w0, f0, rel0, s0);
   eval(k, w1, f1, rel1, s1);
   for (int it = 0; it < n_iter; ++it) {
-    const cx df = f1 - f0;
-    cx w2 = w1 - f1 * ((w1 - w0) / df);
-    if (!cfinite(w2) || cabs2(df) == 0.0) w2 = w1;          // converged (f1 == f0) or broken: stay
+    const cz df = f1 - f0;
+    cz w2 = w1 - f1 * ((w1 - w0) / df);
+    if (!cz_finite(w2) || cz_abs2(df) == 0.0) w2 = w1;    // converged (f1 == f0) or broken: stay
     w0 = w1; f0 = f1;
     w1 = w2;
     eval(k, w1, f1, rel1, s1);
-    if (!cfinite(f1)) { w1 = w0; f1 = f0; }                 // stepped onto a leaky / singular point: back off
+    if (!cz_finite(f1)) { w1 = w0; f1 = f0; }              // stepped onto a leaky / singular point: back off
   }
   // rel of the final iterate
   eval(k, w1, f1, rel1, s1);
   if (in) {
-    const double dist2 = cabs2(w1 - centre), diag2 = 4.0 * cabs2(half);
+    const double dist2 = cz_abs2(w1 - centre), diag2 = 4.0 * cz_abs2(half);
     tab.d_w_re[i] = w1.re;
     tab.d_w_im[i] = w1.im;
     tab.d_resid[i] = rel1;
@@ -58,7 +58,7 @@ __device__ __forceinline__ void cx_refine_candidate(Eval eval, es_complex_root_t
 // What one evaluation hands the Newton rule: D_c with its derivatives in omega and k (Dk: the final evaluation only), rel in
 // percent and the status.
 struct CxNewtonPoint {
-  cx D, Dw, Dk;
+  cz D, Dw, Dk;
   double rel;
   uint8_t st;
 };
@@ -76,24 +76,24 @@ __device__ __forceinline__ void cx_newton_lane(Step step, Final last, const doub
                                                int32_t* __restrict__ flag_out) {
   const bool in = i < cnt;
   const double k = in ? kv[i] : 1.0;
-  const cx guess = in ? cx{gre[i], gim[i]} : cx{1.0, 0.1};
-  cx w = guess;
+  const cz guess = in ? cz(gre[i], gim[i]) : cz(1.0, 0.1);
+  cz w = guess;
   int iters = 0;
   bool ok = true, active = in;
   for (int it = 0; it < max_iter; ++it) {                      // max_iter is uniform: every lane reaches the vote
     const CxNewtonPoint E = step(k, w);
     if (active) {
-      const cx D = E.D, Dw = E.Dw;
-      if (E.st != ES_PT_OK || !cfinite(D) || !cfinite(Dw) || (Dw.re == 0.0 && Dw.im == 0.0)) {
+      const cz D = E.D, Dw = E.Dw;
+      if (E.st != ES_PT_OK || !cz_finite(D) || !cz_finite(Dw) || (Dw.re == 0.0 && Dw.im == 0.0)) {
         ok = false;
         active = false;
       } else {
-        cx s = -(D / Dw);
-        const double a = cabs_(s);
+        cz s = -(D / Dw);
+        const double a = cz_abs(s);
         if (a > step_cap) s = (step_cap / a) * s;
         w = w + s;
         ++iters;
-        if (cabs_(s) <= 1e-14 * fmax(1.0, cabs_(w))) active = false;
+        if (cz_abs(s) <= 1e-14 * fmax(1.0, cz_abs(w))) active = false;
       }
     }
     if (!__syncthreads_or(active ? 1 : 0)) break;
@@ -101,7 +101,7 @@ __device__ __forceinline__ void cx_newton_lane(Step step, Final last, const doub
   const CxNewtonPoint E = last(k, w);
   if (!in) return;
   const bool good = E.st == ES_PT_OK;
-  const cx slope = good ? -(E.Dk / E.Dw) : cx{NAN, NAN};
+  const cz slope = good ? -(E.Dk / E.Dw) : cz(NAN, NAN);
   wre[i] = w.re;
   wim[i] = w.im;
   resid[i] = E.rel;
@@ -110,7 +110,7 @@ __device__ __forceinline__ void cx_newton_lane(Step step, Final last, const doub
     dwdk[2 * (size_t)i + 1] = slope.im;
   }
   iters_out[i] = iters;
-  flag_out[i] = (ok && good && E.rel < tol_percent && cabs_(w - guess) <= max_shift) ? 1 : 0;
+  flag_out[i] = (ok && good && E.rel < tol_percent && cz_abs(w - guess) <= max_shift) ? 1 : 0;
 }
 
 // Host side of a find_roots call after the problem was accepted.  launch_refine(table, half_re, half_im, n) enqueues the

@@ -1,8 +1,9 @@
 // Slopes and Newton tracing of complex roots of the flow slab (include/eigensolver_amd.h section 12): the two sides of the
 // matching condition of es_complex_eval_points, outer and inner, with their exact derivatives in omega (holomorphic) and k.
-// Tangent-linear (forward-mode) evaluation: the formulas of es_complex_shared.hpp at jet width W = 3 (value, d/d omega,
-// d/dk) for the slopes and W = 2 (value, d/d omega) for the Newton steps.  es_complex.hip runs the same text at W = 1, so
-// row 0 of outer - inner is the D_c of es_complex_eval_points bit for bit.
+// Tangent-linear (forward-mode) evaluation: the formulas of es_complex_shared.hpp at the scalar esb::CJet<2> (value,
+// d/d omega, d/dk; the wavenumber the real pair esb::RealK (k, 1)) for the slopes and esb::CJet<1> (value, d/d omega; k a
+// constant) for the Newton steps.  es_complex.hip runs the same text at esb::cz, so row 0 of outer - inner is the D_c of
+// es_complex_eval_points bit for bit.
 //
 // One (k, omega) pair per lane, 64-thread workgroups, the profile table staged chunk by chunk in LDS (cx_stage_chunk):
 // every lane of a workgroup reaches every barrier.  Lanes past the count march on dummy inputs and store nothing.
@@ -10,6 +11,12 @@
 
 namespace {
 using namespace es_complex_shared;
+using esb::CJet;
+
+// the evaluation at (value, d/d omega, d/dk)
+__device__ __forceinline__ CxMatch<CJet<2>> cx_eval2(const ShootDev& P, int variant, double k, cz w, double* __restrict__ sb) {
+  return cx_eval(P, variant, esb::RealK{k, 1.0}, esb::cjet_variable<2>(w, 0), sb);
+}
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void cx_slopes_kernel(ShootDev P, int variant, const double* __restrict__ kv,
@@ -22,27 +29,28 @@ __global__ __launch_bounds__(64) void cx_slopes_kernel(ShootDev P, int variant, 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < cnt;
   const double k = in ? kv[i] : 1.0;
-  const cx w = in ? cx{wre[i], wim[i]} : cx{1.0, 0.1};
-  const CxMatch<3> E = cx_eval<3>(P, variant, k, w, sb);
+  const cz w = in ? cz(wre[i], wim[i]) : cz(1.0, 0.1);
+  const CxMatch<CJet<2>> E = cx_eval2(P, variant, k, w, sb);
   if (!in) return;
-  const bool good = E.st == ES_PT_OK && jfinite(E.outer) && jfinite(E.inner);
+  const bool good = E.st == ES_PT_OK && all_finite(E.outer) && all_finite(E.inner);
+  const cz eo[3] = {E.outer.v, E.outer.d[0], E.outer.d[1]}, ei[3] = {E.inner.v, E.inner.d[0], E.inner.d[1]};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const size_t o = 2 * ((size_t)c * n + i);
     if (outer) {
-      outer[o] = good ? E.outer.c[c].re : NAN;
-      outer[o + 1] = good ? E.outer.c[c].im : NAN;
+      outer[o] = good ? eo[c].re : NAN;
+      outer[o + 1] = good ? eo[c].im : NAN;
     }
     if (inner) {
-      inner[o] = good ? E.inner.c[c].re : NAN;
-      inner[o + 1] = good ? E.inner.c[c].im : NAN;
+      inner[o] = good ? ei[c].re : NAN;
+      inner[o + 1] = good ? ei[c].im : NAN;
     }
   }
   if (status) status[i] = E.st;
 }
 
 // Newton in omega at fixed k, one guess per lane: the rule of cx_newton_lane (es_complex_roots.hpp) over the slab's evaluation
-// at jet widths 2 (the steps) and 3 (the final point).
+// at CJet<1> (the steps) and CJet<2> (the final point).
 __global__ __launch_bounds__(64) void cx_newton_kernel(ShootDev P, int variant, const double* __restrict__ kv,
                                                        const double* __restrict__ gre, const double* __restrict__ gim, int n,
                                                        const int32_t* __restrict__ d_count, int max_iter, double step_cap,
@@ -55,13 +63,13 @@ __global__ __launch_bounds__(64) void cx_newton_kernel(ShootDev P, int variant, 
   if ((int)(blockIdx.x * blockDim.x) >= cnt) return;           // the whole workgroup lies past the count
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   cx_newton_lane(
-      [&](double k, cx w) {
-        const CxMatch<2> E = cx_eval<2>(P, variant, k, w, sb);
-        return CxNewtonPoint{E.outer.c[0] - E.inner.c[0], E.outer.c[1] - E.inner.c[1], cx{0.0, 0.0}, E.rel, E.st};
+      [&](double k, cz w) {
+        const CxMatch<CJet<1>> E = cx_eval(P, variant, k, esb::cjet_variable<1>(w, 0), sb);
+        return CxNewtonPoint{E.outer.v - E.inner.v, E.outer.d[0] - E.inner.d[0], cz(0.0, 0.0), E.rel, E.st};
       },
-      [&](double k, cx w) {
-        const CxMatch<3> E = cx_eval<3>(P, variant, k, w, sb);
-        return CxNewtonPoint{E.outer.c[0] - E.inner.c[0], E.outer.c[1] - E.inner.c[1], E.outer.c[2] - E.inner.c[2], E.rel, E.st};
+      [&](double k, cz w) {
+        const CxMatch<CJet<2>> E = cx_eval2(P, variant, k, w, sb);
+        return CxNewtonPoint{E.outer.v - E.inner.v, E.outer.d[0] - E.inner.d[0], E.outer.d[1] - E.inner.d[1], E.rel, E.st};
       },
       kv, gre, gim, i, cnt, max_iter, step_cap, max_shift, tol_percent, wre, wim, resid, dwdk, iters_out, flag_out);
 }

@@ -19,16 +19,15 @@ using namespace es_cyl_complex_shared;
 // The evaluation at the plain complex scalar, as the kernels below take it: D_c = outer - inner, NaN unless st == ES_PT_OK.
 // Every lane of the workgroup must call this.
 template <int F>
-__device__ __forceinline__ void cylc_point(const ShootDev& P, double k, cx wc, cx& D, cx& outer, cx& inner, double& rel,
+__device__ __forceinline__ void cylc_point(const ShootDev& P, double k, cz w, cz& D, cz& outer, cz& inner, double& rel,
                                            uint8_t& st, double* __restrict__ sb) {
-  const CylcMatch<cz> M = cyl_shoot_point<cz, double, F>(P, k, cz(wc.re, wc.im), sb);
-  const cz d = M.outer - M.inner;
+  const CylcMatch<cz> M = cyl_shoot_point<cz, double, F>(P, k, w, sb);
   st = M.st;
   rel = M.rel;
-  outer = cx{M.outer.re, M.outer.im};
-  inner = cx{M.inner.re, M.inner.im};
-  D = cx{d.re, d.im};
-  if (st != ES_PT_OK) { D = cx{NAN, NAN}; outer = D; inner = D; }
+  outer = M.outer;
+  inner = M.inner;
+  D = M.outer - M.inner;
+  if (st != ES_PT_OK) { D = cz(NAN, NAN); outer = D; inner = D; }
 }
 
 // grid (n_re > 0: index -> (row, i_im, i_re)) or point list (n_re == 0); outer_o / inner_o: interleaved complex, may be null
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(256) void cylc_eval_kernel(ShootDev P, const double
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;
   double k = 1.0;
-  cx w = cx{1.0, 0.1};
+  cz w = cz(1.0, 0.1);
   if (in) {
     if (n_re > 0) {
       const long row = i / ((long)n_re * n_im);
@@ -53,10 +52,10 @@ __global__ __launch_bounds__(256) void cylc_eval_kernel(ShootDev P, const double
       w = cx_pick_w(w_mode, k, wre[ire], wim[iim]);
     } else {
       k = kv[i];
-      w = cx{wre[i], wim[i]};
+      w = cz(wre[i], wim[i]);
     }
   }
-  cx D, outer, inner; double rel; uint8_t st;
+  cz D, outer, inner; double rel; uint8_t st;
   cylc_point<F>(P, k, w, D, outer, inner, rel, st, sb);
   if (in) {
     Dre[i] = D.re;
@@ -89,11 +88,11 @@ __global__ __launch_bounds__(64) void cylc_refine_kernel(ShootDev P, es_complex_
     ES_V(half_re); ES_V(half_im); ES_V(n);
   }
   cx_refine_candidate(
-      [&](double k, cx w, cx& f, double& rel, uint8_t& st) {
-        cx outer, inner;
+      [&](double k, cz w, cz& f, double& rel, uint8_t& st) {
+        cz outer, inner;
         decltype(auto) Q = cyl_own_counts<F>(P);
         if constexpr (cyl_uniforms_in_vgprs<F>)
-          if (!(i < n)) w = cx{1.0, 0.1};                      // past the count: the dummy point
+          if (!(i < n)) w = cz(1.0, 0.1);                      // past the count: the dummy point
         cylc_point<F>(Q, k, w, f, outer, inner, rel, st, sb);
       },
       tab, half_re, half_im, i, n, n_iter, tol_percent);

@@ -19,11 +19,9 @@ using esb::CJet;
 
 // the evaluation at (value, d/d omega, d/dk)
 template <int F>
-__device__ __forceinline__ CylcMatch<CJet<2>> cyljet_eval2(const ShootDev& P, double k, cx w, double* __restrict__ sb) {
-  return cyl_shoot_point<CJet<2>, CJet<2>, F>(P, esb::cjet_variable<2>(cz(k), 1), esb::cjet_variable<2>(cz(w.re, w.im), 0), sb);
+__device__ __forceinline__ CylcMatch<CJet<2>> cyljet_eval2(const ShootDev& P, double k, cz w, double* __restrict__ sb) {
+  return cyl_shoot_point<CJet<2>, CJet<2>, F>(P, esb::cjet_variable<2>(cz(k), 1), esb::cjet_variable<2>(w, 0), sb);
 }
-
-__device__ __forceinline__ cx cx_of(cz a) { return cx{a.re, a.im}; }
 
 template <int F>
 __global__ __launch_bounds__(64) void cyljet_slopes_kernel(ShootDev P, const double* __restrict__ kv,
@@ -37,7 +35,7 @@ __global__ __launch_bounds__(64) void cyljet_slopes_kernel(ShootDev P, const dou
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < cnt;
   const double k = in ? kv[i] : 1.0;
-  const cx w = in ? cx{wre[i], wim[i]} : cx{1.0, 0.1};
+  const cz w = in ? cz(wre[i], wim[i]) : cz(1.0, 0.1);
   const CylcMatch<CJet<2>> E = cyljet_eval2<F>(P, k, w, sb);
   if (!in) return;
   const bool good = E.st == ES_PT_OK;                          // covers a non-finite component of outer or inner
@@ -86,20 +84,19 @@ __global__ __launch_bounds__(64) void cyljet_newton_kernel(ShootDev P, const dou
     ES_V(wre); ES_V(wim); ES_V(resid); ES_V(dwdk); ES_V(iters_out); ES_V(flag_out);
   }
   cx_newton_lane(
-      [&](double k, cx w) {
+      [&](double k, cz w) {
         decltype(auto) Q = cyl_own_counts<F>(P);
         if constexpr (cyl_uniforms_in_vgprs<F>)
-          if (!(i < cnt)) w = cx{1.0, 0.1};                    // past the count: the dummy pair
-        const CylcMatch<CJet<1>> E = cyl_shoot_point<CJet<1>, double, F>(Q, k, esb::cjet_variable<1>(cz(w.re, w.im), 0), sb);
-        return CxNewtonPoint{cx_of(E.outer.v - E.inner.v), cx_of(E.outer.d[0] - E.inner.d[0]), cx{0.0, 0.0}, E.rel, E.st};
+          if (!(i < cnt)) w = cz(1.0, 0.1);                    // past the count: the dummy pair
+        const CylcMatch<CJet<1>> E = cyl_shoot_point<CJet<1>, double, F>(Q, k, esb::cjet_variable<1>(w, 0), sb);
+        return CxNewtonPoint{E.outer.v - E.inner.v, E.outer.d[0] - E.inner.d[0], cz(0.0, 0.0), E.rel, E.st};
       },
-      [&](double k, cx w) {
+      [&](double k, cz w) {
         decltype(auto) Q = cyl_own_counts<F>(P);
         if constexpr (cyl_uniforms_in_vgprs<F>)
-          if (!(i < cnt)) w = cx{1.0, 0.1};
+          if (!(i < cnt)) w = cz(1.0, 0.1);
         const CylcMatch<CJet<2>> E = cyljet_eval2<F>(Q, k, w, sb);
-        return CxNewtonPoint{cx_of(E.outer.v - E.inner.v), cx_of(E.outer.d[0] - E.inner.d[0]),
-                             cx_of(E.outer.d[1] - E.inner.d[1]), E.rel, E.st};
+        return CxNewtonPoint{E.outer.v - E.inner.v, E.outer.d[0] - E.inner.d[0], E.outer.d[1] - E.inner.d[1], E.rel, E.st};
       },
       kv, gre, gim, i, cnt, max_iter, step_cap, max_shift, tol_percent, wre, wim, resid, dwdk, iters_out, flag_out);
 }

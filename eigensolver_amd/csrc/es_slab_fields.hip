@@ -8,6 +8,7 @@
 //                             (np.gradient's three-point formulas) for vort_y
 //   es_slab_field_synthesis   the table of one mode -> frames [t][variable][z][x]; the x stage (search, interpolation)
 //                             once per workgroup, then bound by store bandwidth
+#include "es_bessel_complex.hpp"
 #include "es_field_shared.hpp"
 
 // workgroups (of one wave) es_slab_field_synthesis asks for; a build flag so that tools can time other values
@@ -17,17 +18,9 @@
 
 namespace {
 
-struct cx { double re, im; };
-__device__ __forceinline__ cx operator+(cx a, cx b) { return cx{a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ cx operator-(cx a, cx b) { return cx{a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ cx operator*(cx a, cx b) { return cx{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ cx operator*(double s, cx a) { return cx{s * a.re, s * a.im}; }
-__device__ __forceinline__ cx operator/(cx a, cx b) {
-  const double den = b.re * b.re + b.im * b.im;
-  return cx{(a.re * b.re + a.im * b.im) / den, (a.im * b.re - a.re * b.im) / den};
-}
-__device__ __forceinline__ cx times_i(cx a) { return cx{-a.im, a.re}; }
-__device__ __forceinline__ cx times_minus_i(cx a) { return cx{a.im, -a.re}; }
+using esb::cz;
+__device__ __forceinline__ cz times_i(cz a) { return cz(-a.im, a.re); }
+__device__ __forceinline__ cz times_minus_i(cz a) { return cz(a.im, -a.re); }
 
 // ---- (V, Pf) -> five amplitudes -----------------------------------------------------------------------------------------
 struct SlabPolArgs {
@@ -47,10 +40,10 @@ __global__ __launch_bounds__(256) void slab_field_polarisation_kernel(SlabPolArg
   const size_t i = t / n_tab;
   const int j = (int)(t - i * n_tab);
   const double k = a.k[i];
-  const cx w{a.w_re[i], a.w_im ? a.w_im[i] : 0.0};
-  auto get = [&](const double* p, size_t o) { return a.cplx ? cx{p[2 * o], p[2 * o + 1]} : cx{p[o], 0.0}; };
+  const cz w(a.w_re[i], a.w_im ? a.w_im[i] : 0.0);
+  auto get = [&](const double* p, size_t o) { return a.cplx ? cz(p[2 * o], p[2 * o + 1]) : cz(p[o], 0.0); };
   double x, rho, c2, vA2, U, dU;
-  cx V, Pf;
+  cz V, Pf;
   const bool interior = j >= a.n_ext && j < a.n_ext + a.N;
   if (interior) {
     const int node = j - a.n_ext;
@@ -72,20 +65,20 @@ __global__ __launch_bounds__(256) void slab_field_polarisation_kernel(SlabPolArg
     rho = a.rho_e; c2 = a.ce2; vA2 = a.vAe2; U = a.U_e; dU = 0.0;
   }
   const double S = c2 + vA2, q = c2 / S, cT2 = c2 * vA2 / S, k2 = k * k;
-  const cx Om = w - cx{k * U, 0.0};
-  const cx Om2 = Om * Om;
-  const cx tT = Om2 - cx{k2 * cT2, 0.0};
+  const cz Om = w - k * U;
+  const cz Om2 = Om * Om;
+  const cz tT = Om2 - k2 * cT2;
   if (interior && (a.flags & ES_SLAB_FIELD_SHEAR_PT)) {
-    const cx F = (rho * S) * (tT / (Om2 - cx{k2 * c2, 0.0}));
+    const cz F = (rho * S) * (tT / (Om2 - k2 * c2));
     Pf = Pf + ((F / Om) * ((k * dU) * (V / Om)));
   }
-  const cx VoO = V / Om;
-  const cx xi_x = times_i(VoO);
-  const cx xi_z = ((k * q) * Pf) / (rho * tT);
-  const cx v_z = times_minus_i(Om * xi_z + dU * VoO);
+  const cz VoO = V / Om;
+  const cz xi_x = times_i(VoO);
+  const cz xi_z = ((k * q) * Pf) / (rho * tT);
+  const cz v_z = times_minus_i(Om * xi_z + dU * VoO);
   a.x[t] = x;
   double* A = a.amp + (i * (size_t)ES_SAMP_COUNT * n_tab + j) * 2;
-  auto put = [&](int c, cx v) { A[(size_t)c * n_tab * 2] = v.re; A[(size_t)c * n_tab * 2 + 1] = v.im; };
+  auto put = [&](int c, cz v) { A[(size_t)c * n_tab * 2] = v.re; A[(size_t)c * n_tab * 2 + 1] = v.im; };
   put(ES_SAMP_XI_X, xi_x);
   put(ES_SAMP_XI_Z, xi_z);
   put(ES_SAMP_P_T, times_minus_i(Pf));

@@ -1,7 +1,8 @@
 """CPU-side checks of the code objects of the complex-frequency kernels (no GPU needed, as
-tests/test_refine_hybrid_codeobj.py).  They all run one text, es_complex_shared.hpp, at jet widths 1, 2 and 3: no spilled
-VGPRs and no private segment in any kernel that marches, one wave per SIMD's worth of registers at the most for the slope and
-Newton kernels at __launch_bounds__(64), the LDS of one staged chunk, and every kernel still there under its name.
+tests/test_refine_hybrid_codeobj.py).  They all run one text, es_complex_shared.hpp, at the scalars esb::cz, esb::CJet<1> and
+esb::CJet<2>: no spilled VGPRs and no private segment in any kernel that marches, one wave per SIMD's worth of registers at the
+most for the slope and Newton kernels at __launch_bounds__(64), the LDS of one staged chunk, and every kernel still there under
+its name.
 Metadata only (tools/codeobj_table.py)."""
 import os
 import sys
@@ -16,7 +17,7 @@ pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-
 NEW = ("cx_newton_kernel", "cx_slopes_kernel")
 VALUE_PATH = ("cx_eigen_exterior_kernel", "cx_eigen_interior_kernel", "cx_emit_kernel", "cx_eval_kernel", "cx_flag_kernel",
               "cx_refine_kernel")
-MARCHING_VALUE = ("cx_eval_kernel", "cx_refine_kernel", "cx_eigen_interior_kernel")   # the W = 1 instances
+MARCHING_VALUE = ("cx_eval_kernel", "cx_refine_kernel", "cx_eigen_interior_kernel")   # the esb::cz instances
 CHUNK_LDS = 3 * (2 * 128 + 1) * 8                           # U, U', U'' at the nodes and mid-points of 128 steps
 
 

@@ -89,7 +89,7 @@ def test_value_is_the_determinant_of_eval_points(pool, width, mode, variant):
         print(f"{mode} {variant} width {width} N {N}: worst |(outer - inner) - D_c| / max(|outer|, |inner|) = {err.max():.2e} "
               f"over {len(D)} pairs (bound 1.0e-12)")
         assert err.max() <= 1e-12, (N, err)
-        # one text at jet widths 1 and 3, no contraction: row 0 is the value path's arithmetic, operation for operation
+        # one text at the scalars cz and CJet<2>, no contraction: row 0 is the value path's arithmetic, operation for operation
         assert np.array_equal(g["outer"][0] - g["inner"][0], D), N
 
 
@@ -372,8 +372,8 @@ def test_newton_guards(pool):
 @pytest.mark.parametrize("N", (3, 130))
 def test_newton_without_steps_is_eval_points(pool, N):
     """max_iter = 0 on 65 guesses (one full workgroup and a ragged one), a different k in every lane, the leaky pair among
-    them: w is the guess and resid the rel of es_complex_eval_points at the guesses, bit for bit (one text at jet widths 1
-    and 3); flag = 1 where the point is ES_PT_OK with rel < tol_percent."""
+    them: w is the guess and resid the rel of es_complex_eval_points at the guesses, bit for bit (one text at the scalars
+    cz and CJet<2>); flag = 1 where the point is ES_PT_OK with rel < tol_percent."""
     s = pool.solver(0.9, "sfx", N)
     guess = C.NON_ROOT + 0.004 * np.arange(65) * (1 - 0.5j)
     k = C.K0 + 1e-3 * np.arange(65)
