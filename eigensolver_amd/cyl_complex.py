@@ -17,8 +17,9 @@ import numpy as np
 
 from . import _lib
 from .complex_flow import ComplexTracing, _distinct
-from .shooting import (ShootProblem, W_ABSOLUTE, W_PHASE_SPEED, _frame_chunks, _frames_out,  # noqa: F401
-                       _require_exterior_points, cartesian_var_mask, var_mask)
+from .shooting import (ShootProblem, W_ABSOLUTE, W_PHASE_SPEED, _COMPLEX_TABLES, _cartesian_synthesis,  # noqa: F401
+                       _field_synthesis, _frame_chunks, _require_exterior_points, _vorticity_amplitudes, cartesian_var_mask,
+                       var_mask)
 
 
 class CylinderEvaluation:
@@ -137,16 +138,7 @@ def vorticity_amplitudes(ctx, radius, amp, n_nodes, n_ext, m, k):
     """es_cyl_complex_vorticity_amplitudes on the tables of es_cyl_complex_polarisation (radius [n, n_r] and k [n] float64,
     amp [n, 7, n_r] complex128, CUDA, n_r = n_nodes + n_ext): the three complex radial amplitudes of curl v, vort [n, 3, n_r]
     complex128 in the order _lib.CVORT_NAMES, as shooting.vorticity_amplitudes.  Enqueued on the context's stream."""
-    import torch
-    n, n_r = radius.shape
-    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (n, 7, n_r) and k.shape == (n,)
-    for a, dt in ((radius, torch.float64), (amp, torch.complex128), (k, torch.float64)):
-        assert a.is_cuda and a.dtype == dt and a.is_contiguous()
-    vort = torch.empty((n, 3, n_r), dtype=torch.complex128, device=radius.device)
-    rc = ctx.lib.es_cyl_complex_vorticity_amplitudes(ctx.handle, _lib.ptr(radius), _lib.ptr(amp), n, int(n_nodes), int(n_ext),
-                                                     int(m), _lib.ptr(k), _lib.ptr(vort))
-    _lib.check(ctx.handle, rc)
-    return vort
+    return _vorticity_amplitudes(_COMPLEX_TABLES, ctx, radius, amp, n_nodes, n_ext, m, k)
 
 
 def cartesian_synthesis(ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z, t, variables=None, v_scale=1.0,
@@ -154,22 +146,8 @@ def cartesian_synthesis(ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z
     """es_cyl_complex_cartesian_synthesis for the tables of one mode (radius [n_r] float64, amp [7, n_r] and vort [3, n_r]
     complex128 or None, CUDA; w complex): float32 frames out[n_t, n_sel, n_z, n_y, n_x] in the order of
     cartesian_var_mask(variables)[1], as shooting.cartesian_synthesis.  Enqueued on the context's stream; returns (out, names)."""
-    import torch
-    mask, names = cartesian_var_mask(variables)
-    n_r = radius.numel()
-    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (7, n_r) and (vort is None or vort.shape == (3, n_r))
-    for a, dt in ((radius, torch.float64), (amp, torch.complex128), (vort, torch.complex128), (x, torch.float64),
-                  (y, torch.float64), (z, torch.float64), (t, torch.float64)):
-        assert a is None or (a.is_cuda and a.dtype == dt and a.is_contiguous())
-    out = _frames_out(out, (t.numel(), len(names), z.numel(), y.numel(), x.numel()), radius.device)
-    w = complex(w)
-    rc = ctx.lib.es_cyl_complex_cartesian_synthesis(ctx.handle, _lib.ptr(radius), _lib.ptr(amp),
-                                                    _lib.ptr(vort) if vort is not None else None, int(n_nodes), int(n_ext),
-                                                    int(m), float(k), w.real, w.imag, _lib.ptr(x), x.numel(), _lib.ptr(y),
-                                                    y.numel(), _lib.ptr(z), z.numel(), _lib.ptr(t), t.numel(), mask,
-                                                    float(v_scale), float(fill), int(flags), _lib.ptr(out))
-    _lib.check(ctx.handle, rc)
-    return out, names
+    return _cartesian_synthesis(_COMPLEX_TABLES, ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z, t, variables, v_scale,
+                                fill, flags, out)
 
 
 class CylinderEigenfunctions:
@@ -234,19 +212,9 @@ class CylinderEigenfunctions:
         """es_cyl_complex_field_synthesis for the amplitude table of one mode (radius [n_r] float64, amp [7, n_r] complex128,
         CUDA; w complex): float32 frames out[n_t, n_sel, n_z, n_theta, n_r] and, with want_points, points[n_z, n_theta, n_r, 3],
         as shooting.field_synthesis.  Returns (out, points, names)."""
-        import torch
-        mask, names = var_mask(variables)
-        n_r, n_theta, n_z, n_t = radius.numel(), theta.numel(), z.numel(), t.numel()
-        assert amp.shape == (7, n_r) and amp.dtype == torch.complex128 and amp.is_contiguous() and radius.dtype == torch.float64
-        out = _frames_out(out, (n_t, len(names), n_z, n_theta, n_r), radius.device)
-        pts = torch.empty((n_z, n_theta, n_r, 3), dtype=torch.float32, device=radius.device) if want_points else None
-        w = complex(w)
-        rc = self.ctx.lib.es_cyl_complex_field_synthesis(self.ctx.handle, _lib.ptr(radius), _lib.ptr(amp), n_r, int(m), float(k),
-                                                         w.real, w.imag, _lib.ptr(theta), n_theta, _lib.ptr(z), n_z,
-                                                         _lib.ptr(t), n_t, mask, float(v_scale), int(flags),
-                                                         _lib.ptr(pts) if want_points else None, _lib.ptr(out))
-        _lib.check(self.ctx.handle, rc)
-        return out, pts, names
+        assert amp.is_contiguous()
+        return _field_synthesis(_COMPLEX_TABLES, self.ctx, radius, amp, m, k, w, theta, z, t, variables, v_scale, flags,
+                                want_points, out)
 
     def fields(self, mode, k, w, theta, z, t, variables=None, v_scale=1.0, big_endian=False, frames_per_call=None, n_ext=500,
                reference_quirks=True, m=None):

@@ -262,18 +262,7 @@ def field_synthesis(ctx, radius, amp, m, k, w, theta, z, t, variables=None, v_sc
     frames out[n_t, n_sel, n_z, n_theta, n_r] in the order of var_mask(variables)[1] and, with want_points, the mesh
     points[n_z, n_theta, n_r, 3].  theta, z, t: CUDA float64 vectors.  `out`: a preallocated contiguous float32 tensor
     of that shape (4-byte alignment suffices).  Enqueued on the context's stream; returns (out, points, names)."""
-    import torch
-    mask, names = var_mask(variables)
-    n_r, n_theta, n_z, n_t = radius.numel(), theta.numel(), z.numel(), t.numel()
-    assert amp.shape == (7, n_r) and amp.dtype == torch.float64 and radius.dtype == torch.float64
-    out = _frames_out(out, (n_t, len(names), n_z, n_theta, n_r), radius.device)
-    pts = torch.empty((n_z, n_theta, n_r, 3), dtype=torch.float32, device=radius.device) if want_points else None
-    rc = ctx.lib.es_cyl_field_synthesis(ctx.handle, _lib.ptr(radius), _lib.ptr(amp), n_r, int(m), float(k), float(w),
-                                        _lib.ptr(theta), n_theta, _lib.ptr(z), n_z, _lib.ptr(t), n_t, mask,
-                                        float(v_scale), int(flags), _lib.ptr(pts) if want_points else None,
-                                        _lib.ptr(out))
-    _lib.check(ctx.handle, rc)
-    return out, pts, names
+    return _field_synthesis(_REAL_TABLES, ctx, radius, amp, m, k, w, theta, z, t, variables, v_scale, flags, want_points, out)
 
 
 def cartesian_var_mask(variables):
@@ -285,16 +274,7 @@ def vorticity_amplitudes(ctx, radius, amp, n_nodes, n_ext, m, k):
     """es_cyl_vorticity_amplitudes on the tables of es_cyl_polarisation (radius [n, n_r], amp [n, 7, n_r], k [n], CUDA
     float64, n_r = n_nodes + n_ext): the five radial amplitudes of curl v, vort [n, 5, n_r] in the order _lib.VORT_NAMES.
     Enqueued on the context's stream."""
-    import torch
-    n, n_r = radius.shape
-    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (n, 7, n_r) and k.shape == (n,)
-    for a in (radius, amp, k):
-        assert a.is_cuda and a.dtype == torch.float64 and a.is_contiguous()
-    vort = torch.empty((n, 5, n_r), dtype=torch.float64, device=radius.device)
-    rc = ctx.lib.es_cyl_vorticity_amplitudes(ctx.handle, _lib.ptr(radius), _lib.ptr(amp), n, int(n_nodes), int(n_ext),
-                                             int(m), _lib.ptr(k), _lib.ptr(vort))
-    _lib.check(ctx.handle, rc)
-    return vort
+    return _vorticity_amplitudes(_REAL_TABLES, ctx, radius, amp, n_nodes, n_ext, m, k)
 
 
 def cartesian_synthesis(ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z, t, variables=None, v_scale=1.0,
@@ -303,19 +283,69 @@ def cartesian_synthesis(ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z
     float64): float32 frames out[n_t, n_sel, n_z, n_y, n_x] in the order of cartesian_var_mask(variables)[1].  x, y, z,
     t: CUDA float64 vectors.  `out`: a preallocated contiguous float32 tensor of that shape (4-byte alignment suffices).
     Enqueued on the context's stream; returns (out, names)."""
+    return _cartesian_synthesis(_REAL_TABLES, ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z, t, variables, v_scale,
+                                fill, flags, out)
+
+
+class _Tables(NamedTuple):
+    """The two kinds of amplitude tables the field entry points of a cylinder mode take, and what differs between their
+    wrappers: real tables at real omega (C ABI sections 7 and 8), complex ones at complex omega (sections 16 and 20)."""
+    prefix: str                                     # <prefix>field_synthesis, vorticity_amplitudes, cartesian_synthesis
+    dtype: str                                      # torch dtype of amp and vort
+    n_vort: int                                     # vorticity channels: _lib.VORT_NAMES / _lib.CVORT_NAMES
+    w_pair: bool                                    # omega goes in as (re, im), not as one double
+
+    def call(self, ctx, name, *args):
+        _lib.check(ctx.handle, getattr(ctx.lib, self.prefix + name)(ctx.handle, *args))
+
+    def w_args(self, w):
+        return (complex(w).real, complex(w).imag) if self.w_pair else (float(w),)
+
+
+_REAL_TABLES = _Tables("es_cyl_", "float64", 5, False)
+_COMPLEX_TABLES = _Tables("es_cyl_complex_", "complex128", 3, True)
+
+
+def _field_synthesis(tables, ctx, radius, amp, m, k, w, theta, z, t, variables, v_scale, flags, want_points, out):
+    import torch
+    mask, names = var_mask(variables)
+    n_r, n_theta, n_z, n_t = radius.numel(), theta.numel(), z.numel(), t.numel()
+    assert amp.shape == (7, n_r) and amp.dtype == getattr(torch, tables.dtype) and radius.dtype == torch.float64
+    out = _frames_out(out, (n_t, len(names), n_z, n_theta, n_r), radius.device)
+    pts = torch.empty((n_z, n_theta, n_r, 3), dtype=torch.float32, device=radius.device) if want_points else None
+    tables.call(ctx, "field_synthesis", _lib.ptr(radius), _lib.ptr(amp), n_r, int(m), float(k), *tables.w_args(w),
+                _lib.ptr(theta), n_theta, _lib.ptr(z), n_z, _lib.ptr(t), n_t, mask, float(v_scale), int(flags),
+                _lib.ptr(pts) if want_points else None, _lib.ptr(out))
+    return out, pts, names
+
+
+def _vorticity_amplitudes(tables, ctx, radius, amp, n_nodes, n_ext, m, k):
+    import torch
+    n, n_r = radius.shape
+    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (n, 7, n_r) and k.shape == (n,)
+    dtype = getattr(torch, tables.dtype)
+    for a, dt in ((radius, torch.float64), (amp, dtype), (k, torch.float64)):
+        assert a.is_cuda and a.dtype == dt and a.is_contiguous()
+    vort = torch.empty((n, tables.n_vort, n_r), dtype=dtype, device=radius.device)
+    tables.call(ctx, "vorticity_amplitudes", _lib.ptr(radius), _lib.ptr(amp), n, int(n_nodes), int(n_ext), int(m),
+                _lib.ptr(k), _lib.ptr(vort))
+    return vort
+
+
+def _cartesian_synthesis(tables, ctx, radius, amp, vort, n_nodes, n_ext, m, k, w, x, y, z, t, variables, v_scale, fill, flags,
+                         out):
     import torch
     mask, names = cartesian_var_mask(variables)
     n_r = radius.numel()
-    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (7, n_r) and (vort is None or vort.shape == (5, n_r))
-    for a in (radius, amp, vort, x, y, z, t):
-        assert a is None or (a.is_cuda and a.dtype == torch.float64 and a.is_contiguous())
+    assert n_r == int(n_nodes) + int(n_ext) and amp.shape == (7, n_r) and (vort is None or vort.shape == (tables.n_vort, n_r))
+    dtype = getattr(torch, tables.dtype)
+    for a, dt in ((radius, torch.float64), (amp, dtype), (vort, dtype), (x, torch.float64), (y, torch.float64),
+                  (z, torch.float64), (t, torch.float64)):
+        assert a is None or (a.is_cuda and a.dtype == dt and a.is_contiguous())
     out = _frames_out(out, (t.numel(), len(names), z.numel(), y.numel(), x.numel()), radius.device)
-    rc = ctx.lib.es_cyl_cartesian_synthesis(ctx.handle, _lib.ptr(radius), _lib.ptr(amp),
-                                            _lib.ptr(vort) if vort is not None else None, int(n_nodes), int(n_ext),
-                                            int(m), float(k), float(w), _lib.ptr(x), x.numel(), _lib.ptr(y), y.numel(),
-                                            _lib.ptr(z), z.numel(), _lib.ptr(t), t.numel(), mask, float(v_scale),
-                                            float(fill), int(flags), _lib.ptr(out))
-    _lib.check(ctx.handle, rc)
+    tables.call(ctx, "cartesian_synthesis", _lib.ptr(radius), _lib.ptr(amp), _lib.ptr(vort) if vort is not None else None,
+                int(n_nodes), int(n_ext), int(m), float(k), *tables.w_args(w), _lib.ptr(x), x.numel(), _lib.ptr(y), y.numel(),
+                _lib.ptr(z), z.numel(), _lib.ptr(t), t.numel(), mask, float(v_scale), float(fill), int(flags), _lib.ptr(out))
     return out, names
 
 

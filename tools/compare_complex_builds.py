@@ -19,6 +19,12 @@ The inputs are the smallest at which these kernels can go wrong, not a workload:
   real slab fields (ShootProblem.slab_polarisation, slab_fields)   a density slab and a flow slab, two pairs each.
   complex cylinder, untwisted and twisted   eval_points (with both sides), find_roots, root_slopes, newton, eigenfunction
       and polarisation at the same sizes.
+  Cartesian sampling, real and complex (sections 8 and 20)   the vorticity amplitudes on tables of (3, 0), (0, 3), (3, 3)
+      and (64, 65) points, m = 0, 1, 3, and with a NaN node; the synthesis on the five small meshes of the GPU tests (one
+      live lane, the ragged narrow path, the wide path) and the 73 x 70 x 137 x 3 split, into an aligned output and one
+      4 bytes past a 16-byte boundary, every variable, two of them and two without a vorticity table, both byte orders,
+      Im omega > 0, < 0 and = 0, and the mesh of ties, origin, hole, far field and NaN with three fill values.  Frames
+      compare as 32-bit patterns, sentinels around them included.
 
 --time R: after the comparison, R timed passes per build over the flow-slab calls, the builds alternating pass by pass in
 this one process; the line (per build: seconds of every pass, calls per pass, median milliseconds per call, over all calls
@@ -184,6 +190,80 @@ def cylinder_calls(ctx, keep_open):
     return calls
 
 
+def cartesian_calls(ctx):
+    """Cartesian sampling, real (section 8) and complex (section 20): the two vorticity-amplitude and the two synthesis
+    calls on the shapes of tests/test_cartesian_gpu.py and tests/test_cyl_complex_cartesian_gpu.py.  Frames are returned
+    as their 32-bit patterns, so that they compare exactly; the tables are finite, so every NaN in a frame is the fill."""
+    import torch
+    from eigensolver_amd import _lib, cyl_complex, shooting
+    from tests.cyl_complex_cartesian_model import complex_table
+    dev = f"cuda:{ctx.device}"
+    T = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)    # noqa: E731
+    families = (("real", shooting, lambda a: np.ascontiguousarray(a.real), (3.7,)),
+                ("complex", cyl_complex, lambda a: a, (3.7 + 0.6j, 3.7 - 0.6j, 3.7 + 0j)))
+    meshes = [(1, 1, 1, 1), (5, 3, 2, 1), (64, 2, 1, 2), (257, 3, 2, 2), (66, 6, 3, 1)]
+    masks = (("all", None, True), ("v_x+vort_y", ["v_x", "vort_y"], True), ("P_T+v_y no vort", ["P_T", "v_y"], False))
+    calls = []
+
+    def frames(mod, tabs, m, k, w, mesh, variables, v_scale, fill, flags, offset):
+        """one synthesis call into a buffer that starts `offset` floats past a 16-byte boundary, sentinels around it"""
+        shape = (len(mesh[3]), len(shooting.cartesian_var_mask(variables)[1]), len(mesh[2]), len(mesh[1]), len(mesh[0]))
+        total = int(np.prod(shape))
+        buf = torch.full((total + 12,), -777.0, dtype=torch.float32, device=dev)
+        off = ((16 - buf.data_ptr() % 16) % 16) // 4 + 4 + offset
+        out = buf[off:off + total].view(shape)
+        assert out.data_ptr() % 16 == 4 * offset
+        mod.cartesian_synthesis(ctx, *tabs, m, k, w, *(T(a) for a in mesh), variables, v_scale, fill, flags, out=out)
+        return {"frames": buf.view(torch.int32).cpu().numpy()}
+
+    def modes(part, n_nodes, n_ext, n):
+        rad, amp = zip(*[complex_table(n_nodes, n_ext, seed=7 + i) for i in range(n)])
+        return np.stack(rad), part(np.stack(amp) * (1.0 + 0.5 * np.arange(n))[:, None, None]), 0.9 + 0.6 * np.arange(n)
+
+    def synth_group(tag, mod, part, ws, n_nodes, n_ext, m, k, mesh, mask_set, v_scale, fills):
+        radius, amp = complex_table(n_nodes, n_ext)
+        d_radius, d_amp = T(radius), T(part(amp))
+        d_vort = mod.vorticity_amplitudes(ctx, d_radius[None], d_amp[None], n_nodes, n_ext, m, T(np.array([k])))[0].contiguous()
+        for w in ws:
+            for mname, variables, with_vort in mask_set:
+                tabs = (d_radius, d_amp, d_vort if with_vort else None, n_nodes, n_ext)
+                for fill in fills:
+                    for flags in (0, _lib.FIELD_BIG_ENDIAN):
+                        for offset in (0, 1):
+                            calls.append((f"{tag} w={w} {mname} fill={fill} flags={flags} offset={offset}",
+                                          lambda mod=mod, tabs=tabs, w=w, variables=variables, fill=fill, flags=flags,
+                                          offset=offset: frames(mod, tabs, m, k, w, mesh, variables, v_scale, fill, flags, offset)))
+
+    for fam, mod, part, ws in families:
+        for n_nodes, n_ext in ((3, 0), (0, 3), (3, 3), (64, 65)):
+            for m in (0, 1, 3):
+                tag = f"cart {fam} N={n_nodes} n_ext={n_ext} m={m}"
+                calls.append((f"{tag} vorticity_amplitudes n=3", lambda mod=mod, part=part, n_nodes=n_nodes, n_ext=n_ext, m=m: host(
+                    mod.vorticity_amplitudes(ctx, *(T(a) for a in modes(part, n_nodes, n_ext, 3)[:2]), n_nodes, n_ext, m,
+                                             T(modes(part, n_nodes, n_ext, 3)[2])))))
+                for shape in meshes:
+                    mesh = tuple(np.linspace(lo, hi, n) for (lo, hi), n in
+                                 zip(((-1.7, 1.9), (-1.6, 1.45), (0.1, 2.3), (0.01, 1.7)), shape))
+                    synth_group(f"{tag} synthesis {shape}", mod, part, ws, n_nodes, n_ext, m, 1.3, mesh, masks, 2.5, (-7.5,))
+        # several planes per piece, several items per workgroup, a group across two frames
+        mesh = (np.linspace(-1.7, 1.9, 73), np.linspace(-1.6, 1.45, 70), np.linspace(0.0, 4.0, 137), np.array([0.01, 0.8, 1.7]))
+        synth_group(f"cart {fam} N=64 n_ext=65 m=2 synthesis (73, 70, 137, 3)", mod, part, ws, 64, 65, 2, 1.3, mesh,
+                    (("xi_z+v_x+vort_y", ["xi_z", "v_x", "vort_y"], True),), 2.5, (-7.5,))
+        # ties on r == r_b, the origin, the hole, the far field and a NaN coordinate
+        mesh = (np.array([-1.0, 0.0, 1.0, 0.05, 3.5, np.nan]), np.array([-1.0, 0.0, 1.0]), np.array([0.0]), np.array([0.0]))
+        synth_group(f"cart {fam} N=7 n_ext=6 m=0 ties", mod, part, (2.0 + 0.3j,) if fam == "complex" else (2.0,), 7, 6, 0, 1.0,
+                    mesh, masks[:1], 1.5, (float("nan"), 0.0, -7.5))
+        # a NaN node reaches the nodes whose stencil holds it
+        for h in range(2 if fam == "complex" else 1):
+            def nan_node(mod=mod, part=part, h=h):
+                radius, amp, k = modes(lambda a: a, 64, 65, 1)
+                for j in (2, 64 + 30):
+                    (amp.real if h == 0 else amp.imag)[0, :, j] = np.nan
+                return host(mod.vorticity_amplitudes(ctx, T(radius), T(part(amp)), 64, 65, 1, T(k)))
+            calls.append((f"cart {fam} N=64 n_ext=65 m=1 vorticity_amplitudes NaN node part {h}", nan_node))
+    return calls
+
+
 KINDS = ("eval_points", "eval_grid", "find_roots", "eigenfunction", "root_slopes", "newton", "polarisation", "fields")
 
 
@@ -227,7 +307,7 @@ def main():
         ctx = _lib.Context(0, lib=_lib.load_variant(path))
         contexts.append(ctx)
         slab[tag] = slab_calls(ctx, keep_open)
-        results[tag] = run(slab[tag] + real_slab_calls(ctx, keep_open) + cylinder_calls(ctx, keep_open))
+        results[tag] = run(slab[tag] + real_slab_calls(ctx, keep_open) + cylinder_calls(ctx, keep_open) + cartesian_calls(ctx))
     assert list(results["a"]) == list(results["b"])
     bad = elements = statuses = 0
     seen = set()
