@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libeigensolver_amd.so")
 # computes, so the interior march is bit-identical to oracle/c/shoot_port.c (tests/test_shoot_gpu.py); never loaded by
 # the product path
 LIB_IEEE = os.path.join(LIBDIR, "libeigensolver_amd_ieee.so")
-# test-only probe of the device math header (tests/devmath/devmath_probe.hip: one Bessel evaluation per thread, measured
+# test-only probe of the device math headers (tests/devmath/devmath_probe.hip: one Bessel evaluation or jet operator per thread, measured
 # against correctly rounded values by tests/test_devmath_gpu.py); same flags as the library, never loaded by the package
 PROBE_SRC = os.path.join(os.path.dirname(HERE), "tests", "devmath", "devmath_probe.hip")
 LIB_PROBE = os.path.join(LIBDIR, "libes_devmath_probe.so")
@@ -80,8 +80,10 @@ def _probe_needs_build():
     if not os.path.exists(LIB_PROBE):
         return True
     t = os.path.getmtime(LIB_PROBE)
-    headers = ("es_bessel.hpp", "es_bessel_complex.hpp", "es_cjet.hpp")
-    return any(os.path.getmtime(s) > t for s in (PROBE_SRC,) + tuple(os.path.join(CSRC, h) for h in headers))
+    # every header of csrc/: the probe includes es_jet2.hpp, which reaches the formula text of the march and its includes
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
+    headers.append(os.path.join(os.path.dirname(HERE), "include", "eigensolver_amd.h"))
+    return any(os.path.getmtime(s) > t for s in [PROBE_SRC] + headers)
 
 
 def _build_probe(verbose):

@@ -29,7 +29,9 @@ NS = 24
 # several rescaling chunks
 CASES = ("CF_flow_kink_N2", "SFG_flow_kink_N2", "CF_flow_kink_N3", "SFG_flow_kink_N3", "CF_flow_kink_N130",
          "SFG_flow_kink_N130", "CF_flow_sausage", "CF_flow_m3", "CF_flow_m5", "CF_flow_kink_target", "CDC_w095_kink",
-         "CR_kink", "CR_sausage", "SD_w15_sausage", "SD_w15_kink", "SFU_sausage")
+         "CR_kink", "CR_sausage", "SD_w15_sausage", "SD_w15_kink", "SFU_sausage") + M.LARGE_GAP
+# the large-gap cases (far field at ten wavelengths) run on real_eigen_model.large_gap_pairs, one pair per target gap
+# mu (R - 1) = 30, 39, 41, 50: both texts of exterior_cylinder, the one without an I pair from 40 on, and exp(-2 gap) just below
 N_DRAWN = 12        # real_eigen_model.pairs(name, N_DRAWN): the first four are the pairs of the slope tests
 # the pairs of a case, as indices into the drawn ones: 0 .. 3 unless a pair lies so close to a singularity that no radius of
 # RADII brings its self-discrepancy below 1e-8; such a pair is replaced by a later draw (never dropped)
@@ -52,7 +54,11 @@ RADIUS = {"CF_flow_kink_N2": (0.02, 0.02, 0.02, 0.02),
           "CR_sausage": (0.02, 0.02, 0.02, 0.02),
           "SD_w15_sausage": (0.02, 0.02, 0.02, 0.02),
           "SD_w15_kink": (0.02, 0.02, 0.02, 0.02),
-          "SFU_sausage": (0.00125, 0.005, 0.02, 0.005)}
+          "SFU_sausage": (0.00125, 0.005, 0.02, 0.005),
+          "LG_flow_kink": (0.02, 0.02, 0.02, 0.02),
+          "LG_flow_sausage": (0.02, 0.02, 0.02, 0.02),
+          "LG_dens_kink": (0.02, 0.02, 0.02, 0.02),
+          "LG_dens_sausage": (0.02, 0.02, 0.02, 0.02)}
 SELF_MEASURED = {"CF_flow_kink_N2": (1.1e-12, 1.3e-13, 2.7e-12, 5.2e-13),
                  "SFG_flow_kink_N2": (3.6e-12, 7.5e-13, 2.1e-13, 1.2e-14),
                  "CF_flow_kink_N3": (5.7e-13, 1.3e-13, 9.9e-14, 5.8e-13),
@@ -68,7 +74,11 @@ SELF_MEASURED = {"CF_flow_kink_N2": (1.1e-12, 1.3e-13, 2.7e-12, 5.2e-13),
                  "CR_sausage": (3.6e-13, 6.2e-13, 2e-12, 1.2e-11),
                  "SD_w15_sausage": (7.9e-13, 5.2e-14, 1.3e-13, 1.2e-13),
                  "SD_w15_kink": (1.4e-12, 1.3e-13, 3.8e-14, 1.2e-13),
-                 "SFU_sausage": (4.7e-12, 2.9e-13, 5.7e-14, 4.6e-13)}
+                 "SFU_sausage": (4.7e-12, 2.9e-13, 5.7e-14, 4.6e-13),
+                 "LG_flow_kink": (1.3e-13, 2.1e-12, 6.7e-13, 3.8e-13),
+                 "LG_flow_sausage": (2.7e-13, 5.7e-12, 9e-13, 1.4e-12),
+                 "LG_dens_kink": (2.2e-13, 2e-13, 1.1e-12, 5.4e-13),
+                 "LG_dens_sausage": (1.9e-13, 5.1e-13, 2e-13, 2.7e-13)}
 
 # d2 omega / dk2 of the model at the model's roots against the Richardson-combined central difference of the model's c_g
 # along its own Newton-traced root curve (k +- 1e-3, k +- 5e-4): the worst |difference| / max(1, |curvature|) per case,
@@ -87,9 +97,19 @@ EXTREMUM_BRACKET = (1.8, 2.4)
 
 
 def pairs(name):
+    """(k, w) of a case: the drawn pairs PAIRS selects; the large-gap cases use their four gap-targeted pairs"""
+    if name in M.LARGE_GAP:
+        return M.large_gap_pairs(name)
     k, w = M.pairs(name, N_DRAWN)
     idx = list(PAIRS[name])
     return k[idx], w[idx]
+
+
+def gaps(name):
+    """mu (R - 1) at the pairs of a large-gap case: what exterior_cylinder compares with 40"""
+    prob = M.problem(name)
+    k, w = pairs(name)
+    return np.array([np.sqrt(M.exterior_m_e(prob, kk, ww)) * (prob.L_factor * 2.0 * np.pi / kk - 1.0) for kk, ww in zip(k, w)])
 
 
 def cauchy(name, k, w, radius, ns=NS):
@@ -290,6 +310,8 @@ def golden():
         k, w = pairs(name)
         o, i, d = case_jets(name)
         out["cases"][name] = dict(k=k.tolist(), w=w.tolist(), outer=o.tolist(), inner=i.tolist())
+        if name in M.LARGE_GAP:
+            out["cases"][name]["gap"] = gaps(name).tolist()
     for name in CURVE_CASES:
         k, w, r = curve_roots(name)
         w, cg, q = point(name, k, w, r)

@@ -7,7 +7,9 @@ tests/golden/root_curvature_model.json, so that no model runs beside the GPU):
             of the second-order jets being formed by the first-order operators themselves, bit for bit.
   rows 3-5  the model's second derivatives by Cauchy's formula: 1e-10 of max(|outer_xx|, |inner_xx|) per row, the project's
             bound for the GPU against a NumPy restatement, where the stored self-discrepancy of the pair is <= 1e-11, and
-            10 x that self-discrepancy otherwise.  No pair is left out.
+            10 x that self-discrepancy otherwise.  No pair is left out.  The four large-gap cases (far field at ten
+            wavelengths, mu (R - 1) = 30, 39, 41, 50) take Jet2 through both texts of exterior_cylinder, the one without an
+            I pair from 40 on and exp(-2 gap) just below; all sixteen pairs have a self-discrepancy under 1e-11.
   curvature d2 omega / dk2 at the model's roots against the model's, per case under 10 x the figure the CPU test measured
             between the model and the difference of its own c_g (CURVE_MEASURED): 3.2e-11 to 9.0e-11 of max(1, |q|).
   extrema   the NumPy restatement of the rule, iterate for iterate.
@@ -70,6 +72,9 @@ def test_rows_against_root_slopes_and_the_model(pool, name):
     gp = pool.problem(name)
     g = C.read_golden()["cases"][name]
     k, w = np.array(g["k"]), np.array(g["w"])
+    if name in M.LARGE_GAP:
+        gaps = g["gap"]                                         # mu (R - 1): both texts of exterior_cylinder in one call
+        assert len(gaps) == len(k) and min(gaps) < 40.0 <= max(gaps), gaps
     c, s = gp.root_curvature(k, w), gp.root_slopes(k, w)
     assert tuple(c.outer.shape) == (6, len(k)) and c.status.cpu().tolist() == [0] * len(k) == s.status.cpu().tolist()
     co, ci, so, si = _np(c.outer), _np(c.inner), _np(s.outer), _np(s.inner)

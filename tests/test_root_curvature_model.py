@@ -1,7 +1,8 @@
 """The yardsticks of tests/root_curvature_model.py, pinned on the CPU (no GPU needed).
 
   * every pair's self-discrepancy (Cauchy's formula at the pair's radius against half of it) is what the model file stores,
-    none above 1e-8, at least three pairs per case; value and first derivatives are the complex-step jets of
+    none above 1e-8, at least three pairs per case (the four large-gap cases: the gap-targeted pairs of the slope tests, two
+    on each side of mu (R - 1) = 40, with the gap stored beside them); value and first derivatives are the complex-step jets of
     tests/root_slope_model.py
   * the golden file the GPU tests read is what the model gives, in every field those tests use: the pairs and all six
     rows of their jets, the roots of the curvature check with c_g and q, the extremum's bracket, answer and trace
@@ -36,6 +37,15 @@ def test_self_discrepancy_and_golden(name):
     assert first.max() <= 1e-11
     g = C.read_golden()["cases"][name]
     assert np.array_equal(g["k"], k) and np.array_equal(g["w"], w)
+    if name in C.M.LARGE_GAP:
+        # the pairs are the slope tests' gap-targeted ones, two on each side of the branch of exterior_cylinder at 40
+        gaps = C.gaps(name)
+        far = C.M.problem(name).L_factor * 2.0 * np.pi / k      # R, in units of the tube radius
+        print(f"{name}: gaps {gaps}, exterior arguments mu R {gaps * far / (far - 1.0)}")
+        assert np.array_equal(R.pairs(name)[0], k) and np.array_equal(R.pairs(name)[1], w)
+        assert np.allclose(g["gap"], gaps, rtol=1e-14, atol=0.0) and (gaps < 40.0).sum() == 2 and (gaps >= 40.0).sum() == 2
+    else:
+        assert "gap" not in g
     go, gi = np.array(g["outer"]), np.array(g["inner"])
     assert np.max(np.maximum(np.abs(go[:3] - o[:3]), np.abs(gi[:3] - i[:3])) / np.maximum(np.abs(o[:3]), np.abs(i[:3]))) <= 1e-12
     scale = np.maximum(np.abs(o[3:]), np.abs(i[3:]))
